@@ -1,5 +1,15 @@
 """Benchmark: Msamples/s of the path-tracing hot path (BASELINE.json metric).
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what the headline figure needs and no
+more: set-up, W warm-up steps, K timed steps, the result line.  `--dump-outputs DIR` also writes what
+the last timed step computed (the accumulation sums a caller reads back, float32, as two finite
+arrays: DIR/accum.npy with 0 where a sum is not finite and DIR/accum_nonfinite.npy with a code per
+pixel that says which are not -- the few NaN pixels of generated_scene are the reference's own,
+DESIGN.md §3; the inputs are the same on every run, so two builds can be compared output for
+output).  Everything
+else described below -- the roofline, the CPU baselines and the secondary records -- is measured
+only with `--full`.
+
 Workloads (SURVEY.md §8 config labels; one "step" = one pass of the hot path over the workload):
   C3 (default)  generated_scene.json (484 quadrics + synthetic HDR sky), 1920x1080, 1024 spp
   C2            cornell_box.json, 512x512, 64 spp
@@ -61,6 +71,7 @@ VALU_PEAK_G = SIMDS * CLOCK_HZ / 2 / 1e9   # wave64 VALU instructions per second
 NODE_B, PRIM_B, MAT_B, SKY_B = 32, 96, 40, 64            # SURVEY.md §8(d) per-event bytes
 PIXEL_STATE_B = 16 + 16 + 24 + 24                          # accum RMW + XORWOW state RMW, per pixel per launch
 CHUNK = 8                                                  # spp per render() call (main.cpp:272)
+DUMP_MAX_BYTES = 64 << 20                                  # --dump-outputs writes at most this much
 
 CONFIGS = {
     "C2": {"scene": "cornell_box", "width": 512, "height": 512, "spp": 64},
@@ -75,6 +86,13 @@ def parse_args(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: the roofline (instrumented chunks + PMC "
+                        "profile), the CPU baselines and the secondary records (the options below choose among them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed to DIR/accum.npy (float32, 0 for "
+                        "a non-finite sum) and DIR/accum_nonfinite.npy (per-pixel codes of those); a fixed "
+                        f"seeded sample of the pixels where the two exceed {DUMP_MAX_BYTES >> 20} MB")
     p.add_argument("--config", choices=sorted(CONFIGS), default="C3")
     p.add_argument("--spp", type=int, default=0, help="override the config's spp (multiple of 8)")
     p.add_argument("--scaling", choices=["weak", "strong"], default="strong",
@@ -293,6 +311,23 @@ class Run:
             pt.close()
         return st
 
+    def prime(self):
+        # a plain run: the same two untimed 8-spp chunks on the timed context, for what they leave
+        # behind -- the tile costs, so every timed launch runs in cost order, and pixel RNG streams
+        # 16 samples in -- so that the timed steps and their outputs are those of a --full run.  The
+        # counts are dropped.  (A device group's contexts get their cost order from the warm-up.)
+        if self.mode != "group":
+            self.instrument()
+
+    def outputs(self):
+        """What a caller of the timed path holds after a step: the accumulation sums of the whole
+        image, float32 (H x W x 4), as finite values + the codes of the non-finite ones (finite_split).
+        torchrun: rank 0's gathered framebuffer, None on the others."""
+        if self.dist_on and self.rank != 0:
+            return None
+        values, codes = finite_split(self.full.cpu().numpy() if self.dist_on else self.pt.accum())
+        return {"accum": values, "accum_nonfinite": codes}
+
     def step(self):
         ms = self.pt.render_raw(self.cam, CHUNK, self.chunks, True)
         if self.mode == "group":
@@ -349,6 +384,36 @@ def cold_one_shot(cfg, W, H, spp, local_rank, use_torch, warm_step_s, reps=3):
             "what": "fresh Pathtracer + scene load (untimed), then one render_raw of the whole workload: cost "
                     "pre-pass + device sort + the launch in that order (wall time of the call; median of "
                     f"{reps} fresh contexts); cold_over_warm = its time / the headline's step time"}
+
+
+def finite_split(a):
+    """A float32 image (..., C <= 4) as two finite float32 arrays that together hold all of it but NaN
+    payloads: the values with 0 in place of every non-finite one, and per pixel (..., 1) a code
+    sum_k c_k * 4^k over the channels k, c = 0 finite, 1 NaN, 2 +inf, 3 -inf.  (The reference's
+    LAMBERT_GGX pdf can be 0/0, DESIGN.md §3, so a frame of generated_scene holds a few NaN pixels.)"""
+    import numpy as np
+    assert a.shape[-1] <= 4
+    c = np.isnan(a) * 1 + np.isposinf(a) * 2 + np.isneginf(a) * 3
+    code = (c * (4 ** np.arange(a.shape[-1]))).sum(-1, keepdims=True).astype(np.float32)
+    return np.where(c == 0, a, np.float32(0.0)).astype(np.float32), code
+
+
+def dump_outputs(arrays, directory, limit=DUMP_MAX_BYTES):
+    """--dump-outputs: each array as <directory>/<name>.npy.  Together over `limit` bytes, every
+    array is cut to the same fraction of its pixels (the array as (pixels, channels)), drawn by a
+    fixed seed: the same pixels on every run of the same workload, and the same pixels in arrays of
+    one image."""
+    import numpy as np
+    out = pathlib.Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit:
+            items = a.reshape(-1, a.shape[-1])
+            keep = items.shape[0] * limit // total
+            pick = np.sort(np.random.default_rng(0).choice(items.shape[0], size=keep, replace=False))
+            a = np.ascontiguousarray(items[pick])
+        np.save(out / f"{name}.npy", a)
 
 
 def timed(run, steps, warmup, local_rank, dist_on, use_torch=True):
@@ -420,10 +485,13 @@ def lane_utilisation(st):
 def record(cfg, run, elapsed, kernel_ms, steps, st, n, with_profile=True):
     W, H, spp = run.W, run.H, run.spp
     total_samples = W * H * spp * steps
+    workload = workload_name(cfg, W, H, spp)
+    if st is None:                         # a plain run: no instrumented counts, no roofline
+        return {"value": round(total_samples / elapsed / 1e6, 3), "unit": "Msamples/s",
+                "ms_per_step": round(elapsed * 1e3 / steps, 3), "workload": workload, "roofline": None}
     avg_launch_s = kernel_ms / steps / 1e3
     samples_launch = W * H * spp / n                              # per GPU
     alg = algorithmic_bytes(st) / max(st["samples"], 1) * samples_launch + PIXEL_STATE_B * W * H / n
-    workload = workload_name(cfg, W, H, spp)
     prof, src = load_profile(workload) if with_profile else (None, None)
     if prof is None and with_profile:      # e.g. weak scaling: the same scene's base workload, per sample
         prof, src = load_profile(workload_name(cfg, cfg["width"], cfg["height"], cfg["spp"]))
@@ -504,10 +572,18 @@ def main():
 
     use_torch = mode != "group"        # decided by the process's launch mode, for every record below
     run = Run(cfg, W, H, spp, rank, n, local_rank, args.band_rows, mode)
-    st = stats_all(run.instrument())
+    st = None                          # a plain run keeps no counts: record() leaves the roofline out
+    if args.full:
+        st = stats_all(run.instrument())
+    else:
+        run.prime()
     elapsed, kernel_ms = timed(run, args.steps, args.warmup, local_rank, dist_on, use_torch)
     main_rec = record(cfg, run, elapsed, kernel_ms, args.steps, st, n)
     gather_ms = run.gather_ms
+    if args.dump_outputs:
+        arrays = run.outputs()             # of the last timed step: nothing has run since
+        if rank == 0:
+            dump_outputs(arrays, args.dump_outputs)
     run.close()
     part = {"torchrun": f"{args.band_rows}-row bands interleaved x{n}, one process per GPU, RCCL gather (torch.distributed)",
             "group": f"{args.band_rows}-row bands interleaved x{n}, in-process device group (pt_group_*), RCCL gather",
@@ -583,7 +659,7 @@ def main():
             recs.append(recc)
         return recs
 
-    if args.secondary:
+    if args.full and args.secondary:
         if n == 1:
             recs = []
             if args.config == "C3" and args.call_loop:
@@ -634,7 +710,7 @@ def main():
             recs = [recw]
             recs += strong_records()
             out["secondary"] = recs
-    if rank == 0 and n == 1 and args.cpu_baseline:
+    if args.full and rank == 0 and n == 1 and args.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, cfg, W, H)
     if rank == 0:
         print(json.dumps(out), flush=True)

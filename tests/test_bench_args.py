@@ -53,6 +53,73 @@ def test_headline_is_strong_scaling_by_default():
     assert (c["width"], c["height"], c["spp"]) == (1920, 1080, 1024)
 
 
+def test_plain_run_is_the_default():
+    # a plain run times the headline only; the roofline, CPU baselines and secondary records need --full
+    args = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert args.full is False and args.dump_outputs is None
+    assert (args.steps, args.warmup) == (5, 2)
+    args = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert args.full is True and args.dump_outputs == "out"
+
+
+def test_plain_record_has_the_headline_only():
+    class R:
+        W, H, spp = 64, 32, 16
+
+    cfg = {"scene": "cornell_box"}
+    rec = bench.record(cfg, R(), 0.5, 400.0, 4, None, 1)
+    assert rec["roofline"] is None
+    assert rec["ms_per_step"] == 125.0                      # 0.5 s over 4 steps
+    assert rec["value"] == round(64 * 32 * 16 * 4 / 0.5 / 1e6, 3) and rec["unit"] == "Msamples/s"
+    assert rec["workload"] == bench.workload_name(cfg, 64, 32, 16)
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    import numpy as np
+    a = np.arange(40 * 30 * 4, dtype=np.float32).reshape(40, 30, 4)
+    bench.dump_outputs({"accum": a}, tmp_path / "whole")
+    whole = np.load(tmp_path / "whole" / "accum.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, a)
+    # over the limit: a sample of whole pixels, the same on every run and in both arrays of the
+    # image, within the limit in all
+    b = np.arange(40 * 30, dtype=np.float32).reshape(40, 30, 1)
+    limit = 1000 * 20 + 7
+    for d in ("s1", "s2"):
+        bench.dump_outputs({"accum": a, "accum_nonfinite": b}, tmp_path / d, limit=limit)
+    s1, s2 = np.load(tmp_path / "s1" / "accum.npy"), np.load(tmp_path / "s2" / "accum.npy")
+    t1 = np.load(tmp_path / "s1" / "accum_nonfinite.npy")
+    assert s1.dtype == np.float32 and s1.shape == (1000, 4) and t1.shape == (1000, 1)
+    assert s1.nbytes + t1.nbytes <= limit
+    assert np.array_equal(s1, s2)
+    px = (s1[:, 0] / 4).astype(np.int64)                    # pixel p holds 4p .. 4p + 3
+    assert np.all(np.diff(px) > 0) and px[-1] < 40 * 30     # distinct pixels, in image order
+    assert np.array_equal(s1, a.reshape(-1, 4)[px])
+    assert np.array_equal(t1[:, 0], px)                     # the same pixels
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+
+
+def test_finite_split_keeps_everything_but_nan_payloads():
+    import numpy as np
+    a = np.arange(2 * 3 * 4, dtype=np.float32).reshape(2, 3, 4) - 5.0
+    a[0, 1, 0] = np.nan
+    a[0, 1, 3] = -np.inf
+    a[1, 2, 2] = np.inf
+    values, codes = bench.finite_split(a)
+    assert values.dtype == np.float32 and codes.dtype == np.float32
+    assert values.shape == a.shape and codes.shape == (2, 3, 1)
+    assert np.isfinite(values).all() and np.isfinite(codes).all()
+    want = np.zeros((2, 3, 1), dtype=np.float32)
+    want[0, 1, 0] = 1 + 3 * 64                              # NaN in channel 0, -inf in channel 3
+    want[1, 2, 0] = 2 * 16                                  # +inf in channel 2
+    assert np.array_equal(codes, want)
+    ok = np.isfinite(a)
+    assert np.array_equal(values[ok].view(np.uint32), a[ok].view(np.uint32)) and not values[~ok].any()
+    # and back
+    c = (codes.astype(np.int64) // 4 ** np.arange(4)) % 4
+    back = np.where(c == 1, np.nan, np.where(c == 2, np.inf, np.where(c == 3, -np.inf, values)))
+    assert np.array_equal(back, a, equal_nan=True)
+
+
 def test_gpus_below_one_exits_2(capsys):
     with pytest.raises(SystemExit) as e:
         bench.resolve_mode(0, 1, -1, visible(1))

@@ -5,7 +5,7 @@
 # Steps (each under its own time limit; the script stops at the first failing step):
 #   tests        pytest -m gpu (thread timeouts, one process)
 #   smoke        __graft_entry__.smoke()
-#   bench        python bench.py $BENCH_ARGS                      -> $O/bench.json
+#   bench        python bench.py --full $BENCH_ARGS               -> $O/bench.json
 #   kprof        rocprofv3 --kernel-trace --stats of the bench (headline + C2 only, so the
 #                headline kernel's average is its timed launches') -> $O/prof_bench/
 #   pmc          rocprofv3 --pmc passes (one counter group per run) of the timed launches of the
@@ -33,11 +33,11 @@ for step in "$@"; do
       rc=$?; tail -1 "$O/smoke.log"; fatal $rc smoke;;
     bench)
       echo "== bench ${BENCH_ARGS:-}"
-      timeout -k 10 900 python bench.py ${BENCH_ARGS:-} > "$O/bench.json" 2> "$O/bench.err"
+      timeout -k 10 900 python bench.py --full ${BENCH_ARGS:-} > "$O/bench.json" 2> "$O/bench.err"
       rc=$?; tail -c 400 "$O/bench.json"; echo; fatal $rc bench;;
     kprof)
       echo "== rocprofv3 kernel trace"
-      (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/prof_bench" -o run --output-format csv -- python3 "$R/bench.py" --cpu-baseline 0 --call-loop 0 --cold 0 --extra '') > "$O/prof_bench.log" 2>&1
+      (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/prof_bench" -o run --output-format csv -- python3 "$R/bench.py" --full --cpu-baseline 0 --call-loop 0 --cold 0 --extra '') > "$O/prof_bench.log" 2>&1
       rc=$?; tail -1 "$O/prof_bench.log"; fatal $rc rocprof;;
     pmc)
       i=0
