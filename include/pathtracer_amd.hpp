@@ -199,6 +199,19 @@ public:
     // `chunks` successive render(camera, spp, ...) calls in one launch (first one honours
     // ignoreHistory); bit-identical to the loop.  Timing covers the whole launch.
     void renderChunks(const Camera& camera, uint32_t spp, uint32_t chunks, bool ignoreHistory);
+    // Adaptive sampling (pt_render_adaptive, pt_hip.h): calls of spp samples per pixel until the
+    // standard error of the pixel's per-call luminance is below tolerance x (|mean| + floor), at least
+    // minCalls and at most maxCalls calls.  Afterwards getHDRImageData / getImageData divide every
+    // pixel by its own number of calls, and render(..., ignoreHistory = false) is an error until a
+    // render with ignoreHistory starts a uniform buffer again.  Single device only.
+    struct AdaptiveResult {
+        uint32_t rounds;      // trace launches
+        uint64_t samples;     // camera paths traced
+        float gpuMs;
+    };
+    AdaptiveResult renderAdaptive(const Camera& camera, uint32_t spp, uint32_t minCalls, uint32_t maxCalls, float tolerance,
+                                  float floor = 0.01f, bool reset = true);
+    bool adaptive() const { return m_adaptive; }     // the buffer holds an adaptive render
     float getTiming() const;
     uint32_t loadTexture(const char* path);
     void setSkyboxTextureHandle(uint32_t handle);
@@ -230,6 +243,7 @@ private:
     pt_context* m_ctx = nullptr;
     pt_group* m_group = nullptr;
     float m_gatherMs = 0.0f;
+    bool m_adaptive = false;
     BVH m_bvh;
     void allocHostBuffers();
     void check(int rc, const char* what) const;
@@ -250,6 +264,8 @@ struct Params {
     // additions
     unsigned int m_chunk = 8;        // samples per render() call of the headless loop (main.cpp:272)
     bool m_singleLaunch = true;      // run all chunks in one launch (bit-identical; CLI -call_loop: false)
+    float m_adaptive = -1.0f;        // CLI -adaptive <tolerance>: >= 0 renders adaptively, m_spp is the budget
+    unsigned int m_minSpp = 0;       // CLI -minspp: samples every pixel gets (0 = two calls)
 };
 
 Camera loadScene(Pathtracer& pathtracer, const Params& params);

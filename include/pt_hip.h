@@ -175,6 +175,55 @@ PT_API int pt_render(pt_context *ctx, const pt_camera *camera, uint32_t spp, uin
 PT_API int pt_render_instrumented(pt_context *ctx, const pt_camera *camera, uint32_t spp, uint32_t chunks,
                            int ignore_history, float *gpu_ms, pt_render_stats *stats);
 
+/* ---- Adaptive sampling ------------------------------------------------------------------------
+ * "Render until the noise is below a tolerance, at most max_calls x spp samples per pixel."  A pixel
+ * advances in render() calls of spp samples from its own XORWOW stream, so a pixel that stops after n
+ * calls holds exactly the accumulation value and RNG state n reference render(camera, spp, ...) calls
+ * leave.  Next to them the context keeps per pixel m1, m2 (float) and n (calls folded); at the end of
+ * every call, with S the call's colour sum, in exactly these float operations (no contraction):
+ *     y = (0.2126f*S.x + 0.7152f*S.y) + 0.0722f*S.z;   m1 = m1 + y;   m2 = m2 + y*y;   n = n + 1
+ * After every round each pixel is re-evaluated (the batch-means standard error of the per-call
+ * luminance against tolerance x (|mean| + floor)):
+ *     k = (float)n;  mean = m1 / k;  ss = m2 - m1*mean;  if (ss < 0) ss = 0
+ *     se2 = ss / (k*(k - 1));  t = tolerance * (fabsf(mean) + floor)
+ *     conv = tolerance > 0 && ((se2 <= t*t) || !isfinite(m2))
+ *     active = n < min_calls || (n < max_calls && any pixel q of the 3x3 neighbourhood, clipped to the
+ *              context's rows and width, has n_q >= min_calls && !conv_q)
+ * and every active pixel runs one more call (a step).  The render ends when no pixel is active or
+ * when max_calls steps have been made since the reset (steps made by earlier renders count, so a
+ * render to max_calls = 4 continued with reset = 0 to 8 is the render to 8).  The rule has no memory:
+ * a stopped pixel can start again, and n ends anywhere in [min_calls, max_calls].  Non-finite
+ * pixels count as converged (more samples cannot repair them); tolerance = 0 never converges: the
+ * result is pt_render(spp, max_calls, 1)'s plus the moments.
+ * reset != 0: a pixel's first call overwrites its accumulation value (as ignore_history does) and
+ * starts from zero moments.  reset = 0 continues from the stored moments; PT_ERR_STATE when there are
+ * none (no adaptive render since the last pt_render, pt_write_rng or scene, texture or sky change).
+ * The kernel variant set by pt_set_kernel_variant is honoured when it has an adaptive build (0, 4, 6,
+ * 40, 41, 46, 60, 61); otherwise PT_ERR_ARG.  All builds produce identical results. */
+typedef struct pt_adaptive_params {
+    uint32_t spp;          /* samples per call, >= 1 */
+    uint32_t min_calls;    /* >= 2 */
+    uint32_t max_calls;    /* >= min_calls */
+    float tolerance;       /* >= 0 */
+    float floor;           /* >= 0 */
+    int reset;
+} pt_adaptive_params;
+
+typedef struct pt_adaptive_result {
+    uint32_t rounds;       /* trace launches (the first min_calls calls of a reset render are one) */
+    uint64_t samples;      /* camera paths traced */
+    float gpu_ms;          /* hipEvent time of the whole render, evaluation passes included */
+} pt_adaptive_result;
+
+PT_API int pt_render_adaptive(pt_context *ctx, const pt_camera *camera, const pt_adaptive_params *params,
+                              pt_adaptive_result *result);
+/* Moments of the last adaptive render: rows x width x 3 (m1, m2, n -- n as uint32 bits). */
+PT_API int pt_read_moments(pt_context *ctx, float *dst);
+/* accum / (float)n per pixel (rows x width float4): getHDRImageData's units with frames = calls. */
+PT_API int pt_read_adaptive_hdr(pt_context *ctx, float *dst);
+/* pt_tonemap with every pixel divided by its own n (RGBA8, rows x width). */
+PT_API int pt_tonemap_adaptive(pt_context *ctx, uint8_t *dst);
+
 /* Raw accumulation sums (float4 per local pixel, rows x width, y-up), the data behind
  * getHDRImageData (Pathtracer.cpp:299-315) before the division by the frame count. */
 PT_API int pt_read_accum(pt_context *ctx, float *dst);

@@ -71,6 +71,14 @@ PT_API void pth_renderer_destroy(pth_renderer *r);
 PT_API int pth_renderer_load_scene(pth_renderer *r, const char *path, pt_camera *camera);
 /* `chunks` x Pathtracer::render(camera, spp, ignore_history && first) in one launch. */
 PT_API int pth_renderer_render(pth_renderer *r, const pt_camera *camera, uint32_t spp, uint32_t chunks, int ignore_history);
+/* Pathtracer::renderAdaptive (pt_render_adaptive, pt_hip.h; single device).  Afterwards
+ * pth_renderer_hdr / pth_renderer_image divide every pixel by its own number of calls, and
+ * pth_renderer_render with ignore_history = 0 returns PT_ERR_STATE until a render with
+ * ignore_history != 0 starts a uniform buffer again.  pth_renderer_adaptive: 1 while the buffer holds
+ * an adaptive render. */
+PT_API int pth_renderer_render_adaptive(pth_renderer *r, const pt_camera *camera, const pt_adaptive_params *params,
+                                        pt_adaptive_result *result);
+PT_API int pth_renderer_adaptive(const pth_renderer *r);
 PT_API float pth_renderer_timing(const pth_renderer *r);
 PT_API uint32_t pth_renderer_frames(const pth_renderer *r);
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer *r);

@@ -215,6 +215,53 @@ class Pathtracer:
         """`chunks` x render(camera, spp, ignore_history and first) in one kernel launch."""
         N.check_host(N.host().pth_renderer_render(self._r, C.byref(camera), int(spp), int(chunks), int(bool(ignore_history))))
 
+    # --- adaptive sampling (pt_render_adaptive, pt_hip.h) -----------------------------------------
+    def render_adaptive(self, camera: PtCamera, spp: int, min_calls: int, max_calls: int, tolerance: float,
+                        floor: float = 0.01, reset: bool = True) -> Dict[str, float]:
+        """Render calls of `spp` samples per pixel until the standard error of a pixel's per-call
+        luminance is below tolerance x (|mean| + floor): at least `min_calls`, at most `max_calls`
+        calls.  A pixel stopped after n calls holds what n render(camera, spp, ...) calls leave.
+        Afterwards get_hdr_image_data() / get_image_data() divide every pixel by its own n; see also
+        moments(), sample_counts(), noise_map().  reset=False continues the previous adaptive render.
+        Returns {"rounds", "samples", "gpu_ms", "mean_spp"}."""
+        self._single("render_adaptive")
+        ap = N.PtAdaptiveParams(int(spp), int(min_calls), int(max_calls), float(tolerance), float(floor), int(bool(reset)))
+        res = N.PtAdaptiveResult()
+        N.check_host(N.host().pth_renderer_render_adaptive(self._r, C.byref(camera), C.byref(ap), C.byref(res)))
+        npix = max(1, self.rows * self.width)
+        return {"rounds": int(res.rounds), "samples": int(res.samples), "gpu_ms": float(res.gpu_ms),
+                "mean_spp": int(res.samples) / npix}
+
+    @property
+    def adaptive(self) -> bool:
+        """The buffer holds an adaptive render (pixels with different numbers of calls)."""
+        return bool(N.host().pth_renderer_adaptive(self._r))
+
+    def moments(self) -> np.ndarray:
+        """Per-pixel luminance moments of the last adaptive render: rows x width x 3 float32 (m1, m2,
+        and n as uint32 bits -- sample_counts() gives it as integers)."""
+        self._single("moments")
+        out = np.zeros((self.rows, self.width, 3), dtype=np.float32)
+        N.check_ctx(N.hip().pt_read_moments(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float))), self._ctx)
+        return out
+
+    def sample_counts(self) -> np.ndarray:
+        """render() calls folded into each pixel by the last adaptive render (rows x width uint32)."""
+        return np.ascontiguousarray(self.moments()[..., 2]).view(np.uint32)
+
+    def noise_map(self) -> np.ndarray:
+        """Relative standard error of each pixel's mean per-call luminance (rows x width float32):
+        sqrt(max(m2 - m1^2 / n, 0) / (n (n - 1))) / |m1 / n|; 0 where the mean is 0, NaN where the
+        pixel is not finite or has fewer than 2 calls."""
+        m = self.moments()
+        n = self.sample_counts().astype(np.float32)
+        with np.errstate(all="ignore"):
+            mean = m[..., 0] / n
+            se = np.sqrt(np.maximum(m[..., 1] - m[..., 0] * mean, 0) / (n * (n - 1)))
+            out = np.where(mean == 0, np.float32(0), se / np.abs(mean)).astype(np.float32)
+        out[n < 2] = np.nan
+        return out
+
     def get_timing(self) -> float:
         return float(N.host().pth_renderer_timing(self._r))
 

@@ -51,6 +51,16 @@ class PtRenderStats(C.Structure):
                 ("family_execs_compacted_in_round", C.c_uint64), ("repairs", C.c_uint64)]
 
 
+class PtAdaptiveParams(C.Structure):
+    """pt_adaptive_params (pt_hip.h, adaptive sampling)."""
+    _fields_ = [("spp", C.c_uint32), ("min_calls", C.c_uint32), ("max_calls", C.c_uint32), ("tolerance", C.c_float),
+                ("floor", C.c_float), ("reset", C.c_int)]
+
+
+class PtAdaptiveResult(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("samples", C.c_uint64), ("gpu_ms", C.c_float)]
+
+
 # symbol -> (restype, argtypes); the CPU test suite checks that every declaration in include/*.h
 # is exported and bound here.
 P = C.POINTER
@@ -66,6 +76,10 @@ _HIP_SYMBOLS = {
     "pt_render": (C.c_int, [C.c_void_p, P(PtCamera), C.c_uint32, C.c_uint32, C.c_int, P(C.c_float)]),
     "pt_render_instrumented": (C.c_int, [C.c_void_p, P(PtCamera), C.c_uint32, C.c_uint32, C.c_int, P(C.c_float),
                                          P(PtRenderStats)]),
+    "pt_render_adaptive": (C.c_int, [C.c_void_p, P(PtCamera), P(PtAdaptiveParams), P(PtAdaptiveResult)]),
+    "pt_read_moments": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_read_adaptive_hdr": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_tonemap_adaptive": (C.c_int, [C.c_void_p, P(C.c_uint8)]),
     "pt_read_accum": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "pt_copy_accum_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "pt_tonemap": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint8)]),
@@ -137,6 +151,8 @@ _HOST_SYMBOLS = {
     "pth_renderer_destroy": (None, [C.c_void_p]),
     "pth_renderer_load_scene": (C.c_int, [C.c_void_p, C.c_char_p, P(PtCamera)]),
     "pth_renderer_render": (C.c_int, [C.c_void_p, P(PtCamera), C.c_uint32, C.c_uint32, C.c_int]),
+    "pth_renderer_render_adaptive": (C.c_int, [C.c_void_p, P(PtCamera), P(PtAdaptiveParams), P(PtAdaptiveResult)]),
+    "pth_renderer_adaptive": (C.c_int, [C.c_void_p]),
     "pth_renderer_timing": (C.c_float, [C.c_void_p]),
     "pth_renderer_frames": (C.c_uint32, [C.c_void_p]),
     "pth_renderer_local_rows": (C.c_uint32, [C.c_void_p]),

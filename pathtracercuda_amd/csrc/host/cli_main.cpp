@@ -6,6 +6,10 @@
 //   -call_loop     one kernel launch per render() call, as main.cpp:272-279 (the default runs all
 //                  render() calls of the loop in one launch: bit-identical and 1.37x faster at
 //                  1080p x 1024 spp; -single_launch is accepted for compatibility)
+//   -adaptive T    adaptive sampling (Pathtracer::renderAdaptive): calls of -chunk samples per pixel
+//                  until the standard error of the pixel's luminance is below T x (|mean| + 0.01);
+//                  -spp is the budget (at most spp / chunk calls), -minspp N the samples every pixel
+//                  gets (default two calls).  One GPU.
 // The windowed / interactive mode (-window, -enable_controls) is not supported.
 #include <algorithm>
 #include <cstdio>
@@ -63,6 +67,15 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
         if (strcmp(argv[i], "-chunk") == 0) { uintArg(i, "-chunk", params.m_chunk); i += 2; continue; }
         if (strcmp(argv[i], "-single_launch") == 0) { params.m_singleLaunch = true; ++i; continue; }
         if (strcmp(argv[i], "-call_loop") == 0) { params.m_singleLaunch = false; ++i; continue; }
+        if (strcmp(argv[i], "-adaptive") == 0) {
+            char* end = nullptr;
+            const float t = i + 1 < argc ? strtof(argv[i + 1], &end) : -1.0f;
+            if (i + 1 >= argc || end == argv[i + 1] || !(t >= 0.0f)) { printf("Invalid input for -adaptive!\n"); displayHelp = true; }
+            else params.m_adaptive = t;
+            i += 2;
+            continue;
+        }
+        if (strcmp(argv[i], "-minspp") == 0) { uintArg(i, "-minspp", params.m_minSpp); i += 2; continue; }
         printf("Can't parse argument: %s\n", argv[i]);
         displayHelp = true;
         break;
@@ -86,6 +99,8 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
         printf("%-30s Render on N GPUs (row bands interleaved, RCCL gather)\n", "-gpus");
         printf("%-30s Samples per render() call (default 8)\n", "-chunk");
         printf("%-30s One kernel launch per render() call (default: all calls in one launch)\n", "-call_loop");
+        printf("%-30s Adaptive sampling to this relative noise tolerance; -spp is the budget\n", "-adaptive");
+        printf("%-30s Samples every pixel gets with -adaptive (default two calls)\n", "-minspp");
         return false;
     }
     params.m_enableControls = params.m_enableControls && params.m_showWindow;
@@ -119,6 +134,11 @@ int main(int argc, char* argv[])
         return EXIT_FAILURE;
     }
     gpus = std::max(1, std::min(gpus, available));
+    const bool adaptive = params.m_adaptive >= 0.0f;
+    if (adaptive && gpus > 1) {
+        printf("-adaptive renders on one GPU; ignoring -gpus.\n");
+        gpus = 1;
+    }
     // main.cpp:263 constructs one Pathtracer on device 0; -gpus N spans N devices with the same
     // interface (row bands over the devices, RCCL gather to device 0 when the image is read)
     std::unique_ptr<Pathtracer> pathtracer;
@@ -134,7 +154,16 @@ int main(int argc, char* argv[])
     // headless loop (main.cpp:269-288)
     const uint32_t chunk = params.m_chunk;
     float totalGpuTime = 0.0f;
-    if (params.m_singleLaunch && params.m_spp > 0) {
+    if (adaptive) {
+        const uint32_t maxCalls = std::max(2u, params.m_spp / chunk);
+        const uint32_t minCalls = params.m_minSpp ? std::min(maxCalls, std::max(2u, (params.m_minSpp + chunk - 1) / chunk)) : 2u;
+        const Pathtracer::AdaptiveResult res = pathtracer->renderAdaptive(camera, chunk, minCalls, maxCalls, params.m_adaptive);
+        totalGpuTime = res.gpuMs;
+        printf("Adaptive sampling: tolerance %g, %u..%u calls of %u samples, %u launches\n", params.m_adaptive, minCalls,
+               maxCalls, chunk, res.rounds);
+        printf("Finished accumulating %f samples per pixel on average (budget %d) in %f ms GPU time\n",
+               (double)res.samples / ((double)params.m_width * params.m_height), (int)(maxCalls * chunk), totalGpuTime);
+    } else if (params.m_singleLaunch && params.m_spp > 0) {
         const uint32_t full = params.m_spp / chunk, rest = params.m_spp % chunk;
         if (full) { pathtracer->renderChunks(camera, chunk, full, true); totalGpuTime += pathtracer->getTiming(); }
         if (rest) { pathtracer->renderChunks(camera, rest, 1, full == 0); totalGpuTime += pathtracer->getTiming(); }
@@ -149,7 +178,7 @@ int main(int argc, char* argv[])
             if (i % (chunk * 4) == 0) printf("Accumulated %d samples\n", (int)i);
         }
     }
-    printf("Finished accumulating %d samples in %f ms GPU time\n", (int)params.m_spp, totalGpuTime);
+    if (!adaptive) printf("Finished accumulating %d samples in %f ms GPU time\n", (int)params.m_spp, totalGpuTime);
 
     if (params.m_outputFilepath) {
         printf("Writing result to %s\n", params.m_outputFilepath);

@@ -280,22 +280,26 @@ PT_API int pth_renderer_render(pth_renderer* r, const pt_camera* camera, uint32_
 {
     if (!r || !camera) return setError(PT_ERR_ARG, "invalid argument");
     PTH_GUARD_BEGIN
-    Camera cam(vec3(0.0f), vec3(0.0f, 0.0f, -1.0f), vec3(0.0f, 1.0f, 0.0f), 1.0f, 1.0f);
-    cam.m_tanHalfFovy = camera->tan_half_fovy;
-    cam.m_aspectRatio = camera->aspect_ratio;
-    for (int i = 0; i < 3; ++i) {
-        cam.m_origin[i] = camera->origin[i];
-        cam.m_lowerLeftCorner[i] = camera->lower_left_corner[i];
-        cam.m_horizontal[i] = camera->horizontal[i];
-        cam.m_vertical[i] = camera->vertical[i];
-        cam.m_right[i] = camera->right[i];
-        cam.m_up[i] = camera->up[i];
-        cam.m_backward[i] = camera->backward[i];
-    }
-    r->pt->renderChunks(cam, spp, chunks, ignore_history != 0);
+    r->pt->renderChunks(camera_from_device(*camera), spp, chunks, ignore_history != 0);
     return PT_OK;
     PTH_GUARD_END
 }
+
+PT_API int pth_renderer_render_adaptive(pth_renderer* r, const pt_camera* camera, const pt_adaptive_params* params,
+                                        pt_adaptive_result* result)
+{
+    if (result) *result = pt_adaptive_result{};
+    if (!r || !camera || !params) return setError(PT_ERR_ARG, "invalid argument");
+    PTH_GUARD_BEGIN
+    const Pathtracer::AdaptiveResult res = r->pt->renderAdaptive(camera_from_device(*camera), params->spp, params->min_calls,
+                                                                 params->max_calls, params->tolerance, params->floor,
+                                                                 params->reset != 0);
+    if (result) *result = pt_adaptive_result{res.rounds, res.samples, res.gpuMs};
+    return PT_OK;
+    PTH_GUARD_END
+}
+
+PT_API int pth_renderer_adaptive(const pth_renderer* r) { return r && r->pt->adaptive() ? 1 : 0; }
 
 PT_API float pth_renderer_timing(const pth_renderer* r) { return r ? r->pt->getTiming() : 0.0f; }
 PT_API uint32_t pth_renderer_frames(const pth_renderer* r) { return r ? r->pt->accumulatedFrames() : 0; }

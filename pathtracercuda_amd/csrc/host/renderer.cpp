@@ -105,6 +105,12 @@ void Pathtracer::render(const Camera& camera, uint32_t spp, bool ignoreHistory)
 
 void Pathtracer::renderChunks(const Camera& camera, uint32_t spp, uint32_t chunks, bool ignoreHistory)
 {
+    // after renderAdaptive the pixels hold different numbers of calls: one frame counter cannot
+    // normalise a buffer that goes on accumulating (ignoreHistory starts a uniform buffer again)
+    if (m_adaptive && !ignoreHistory)
+        check(PT_ERR_STATE, "render: the buffer holds an adaptive render; continue it with renderAdaptive(reset = false) "
+                            "or start over with ignoreHistory");
+    m_adaptive = false;
     if (ignoreHistory) m_accumulatedFrames = 0;
     m_timing = 0.0f;
     const pt_camera cam = camera.toDevice();
@@ -113,6 +119,22 @@ void Pathtracer::renderChunks(const Camera& camera, uint32_t spp, uint32_t chunk
     else check(pt_render(m_ctx, &cam, spp, chunks, ignoreHistory ? 1 : 0, &ms), "pt_render");
     m_timing = ms;
     m_accumulatedFrames += chunks;
+}
+
+Pathtracer::AdaptiveResult Pathtracer::renderAdaptive(const Camera& camera, uint32_t spp, uint32_t minCalls, uint32_t maxCalls,
+                                                      float tolerance, float floor, bool reset)
+{
+    if (m_group) check(PT_ERR_STATE, "renderAdaptive: not available on a device group");
+    if (!reset && !m_adaptive) check(PT_ERR_STATE, "renderAdaptive: reset = false needs a previous adaptive render");
+    m_timing = 0.0f;
+    const pt_camera cam = camera.toDevice();
+    const pt_adaptive_params ap = {spp, minCalls, maxCalls, tolerance, floor, reset ? 1 : 0};
+    pt_adaptive_result res = {};
+    check(pt_render_adaptive(m_ctx, &cam, &ap, &res), "pt_render_adaptive");
+    m_timing = res.gpu_ms;
+    m_adaptive = true;
+    m_accumulatedFrames = 0;          // the per-pixel counts describe the buffer now
+    return AdaptiveResult{res.rounds, res.samples, res.gpu_ms};
 }
 
 float Pathtracer::getTiming() const { return m_timing; }
@@ -139,6 +161,10 @@ void Pathtracer::setSkyboxTextureHandle(uint32_t handle)
 
 float* Pathtracer::getHDRImageData()
 {
+    if (m_adaptive) {                  // every pixel over its own number of calls
+        check(pt_read_adaptive_hdr(m_ctx, m_cpuAccumBuffer.data()), "pt_read_adaptive_hdr");
+        return m_cpuAccumBuffer.data();
+    }
     if (m_group) {
         check(pt_group_gather(m_group, &m_gatherMs), "pt_group_gather");
         check(pt_group_read_accum(m_group, m_cpuAccumBuffer.data()), "pt_group_read_accum");
@@ -152,6 +178,10 @@ float* Pathtracer::getHDRImageData()
 
 char* Pathtracer::getImageData()
 {
+    if (m_adaptive) {
+        check(pt_tonemap_adaptive(m_ctx, (uint8_t*)m_cpuResultBuffer.data()), "pt_tonemap_adaptive");
+        return m_cpuResultBuffer.data();
+    }
     if (m_group) check(pt_group_tonemap(m_group, m_accumulatedFrames, (uint8_t*)m_cpuResultBuffer.data()), "pt_group_tonemap");
     else check(pt_tonemap(m_ctx, m_accumulatedFrames, (uint8_t*)m_cpuResultBuffer.data()), "pt_tonemap");
     return m_cpuResultBuffer.data();

@@ -301,6 +301,22 @@ PT_DEV PixelCtx pixel_of(const TraceParams& P, uint32_t tile, uint32_t lane)
     return pc;
 }
 
+// MODE 5 (adaptive sampling): lane k of wave w takes entry 64 w + k of the compacted list of active
+// local pixel indices (tile-major, so a wave's pixels stay close); coordinates as the scattered
+// mapping derives them.  The list's last wave is partial.
+PT_DEV PixelCtx pixel_of_list(const TraceParams& P, uint32_t wave, uint32_t lane)
+{
+    PixelCtx pc;
+    pc.npix = (size_t)P.rows * P.width;
+    const uint32_t entry = wave * 64u + lane;
+    pc.valid = entry < P.adCount;
+    pc.li = pc.valid ? P.adList[entry] : 0u;
+    const uint32_t ly = pc.li / P.width;
+    pc.px = pc.li - ly * P.width;
+    pc.py = global_row(ly, P.rowOffset, P.rowStride, P.bandShift);
+    return pc;
+}
+
 // Where the current render() call's colour sum (touched once per sample) and the running
 // accumulation value (touched once per call) live.  CL (the six-wave builds, 80 VGPRs): the colour
 // sum in the wave's LDS slice, the accumulation value in registers -- the register allocator spills
@@ -440,7 +456,26 @@ PT_DEV void ahead_store(const TraceParams& P, const PixelCtx& pc, const f3& colo
 // (trace.cu:193-198).  AHEAD: a lane already in run-ahead (ps.c == chunks) has done a whole next call:
 // it stashes it and stops; a lane finishing its last call stores its pixel now (the call's RNG state
 // and accumulation are final here) and, when the launch makes a stash, goes on with the next call.
-template <bool AHEAD, bool CL>
+// MODE 5 (adaptive sampling): the call's colour sum S folded into the pixel's luminance moments, a
+// global read-modify-write once per call (three words next to the 10 the pixel's load and store move;
+// registers or LDS would hold them live across the call's samples).  The operations and their order
+// are the contract (include/pt_hip.h, pt_render_adaptive): y = (0.2126 S.x + 0.7152 S.y) + 0.0722 S.z,
+// m1 += y, m2 += y * y, n += 1; `fresh`: the pixel's first call of a reset render starts from zero.
+PT_DEV void moments_fold(const TraceParams& P, const PixelCtx& pc, const f3& S, bool fresh)
+{
+    uint32_t li = (uint32_t)pc.li;
+    asm volatile("" : "+v"(li));                 // addresses from one register (store_pixel)
+    uint32_t* M = P.adMom;
+    const float y = (0.2126f * S.x + 0.7152f * S.y) + 0.0722f * S.z;
+    const float m1 = fresh ? 0.0f : __uint_as_float(M[li]);
+    const float m2 = fresh ? 0.0f : __uint_as_float(M[pc.npix + li]);
+    const uint32_t n = fresh ? 0u : M[2 * pc.npix + li];
+    M[li] = __float_as_uint(m1 + y);
+    M[pc.npix + li] = __float_as_uint(m2 + y * y);
+    M[2 * pc.npix + li] = n + 1u;
+}
+
+template <bool AHEAD, bool CL, bool MOM = false>
 PT_DEV void end_call(const TraceParams& P, const PixelCtx& pc, PathState& ps, const Xorwow& rng)
 {
     const f3 color = get_color<CL>(ps);
@@ -450,6 +485,7 @@ PT_DEV void end_call(const TraceParams& P, const PixelCtx& pc, PathState& ps, co
         return;
     }
     const bool ignore = (ps.c == 0) && P.ignoreFirst;
+    if (MOM) moments_fold(P, pc, color, ignore);
     set_accum<CL>(ps, ignore ? color : add(color, get_accum<CL>(ps)));
     set_color<CL>(ps, splat(0.0f));
     ps.s = 0;
@@ -463,14 +499,14 @@ PT_DEV void end_call(const TraceParams& P, const PixelCtx& pc, PathState& ps, co
     }
 }
 
-template <bool STATS, bool AHEAD, bool CL>
+template <bool STATS, bool AHEAD, bool CL, bool MOM = false>
 PT_DEV void finish_path(const TraceParams& P, PathState& ps, Xorwow& rng, float fx, float fy, Counters& cnt,
                         const PixelCtx& pc)
 {
     const f3 color = add(get_color<CL>(ps), ps.L);
     set_color<CL>(ps, color);
     if (STATS) cnt.samples++;
-    if (++ps.s == P.spp) end_call<AHEAD, CL>(P, pc, ps, rng);
+    if (++ps.s == P.spp) end_call<AHEAD, CL, MOM>(P, pc, ps, rng);
     else if (AHEAD && ps.c == P.chunks) ahead_store(P, pc, color, ps.s, rng);   // a next-call sample
     if (ps.alive) {
         camera_ray(P, fx, fy, rng, ps.o, ps.d);

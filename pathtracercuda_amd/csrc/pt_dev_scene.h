@@ -80,6 +80,12 @@ struct TraceParams {
     uint32_t spreadCU;          // persistent grids of CU-count multiples: the CU count (spread_slot), else 0
     uint32_t prioDealt;         // host only: persistent grids raise the first band to every position dealt
                                 // at the start (launch_one; automatic priority)
+    // MODE 5 (adaptive sampling, pt_render_adaptive): a wave takes 64 entries of a compacted list of
+    // active local pixel indices (slot = wave index; order is null), and every render() call of a pixel
+    // folds its luminance into the pixel's moments (end_call).
+    const uint32_t* adList;     // [adCount] local pixel indices, tile-major
+    uint32_t adCount;
+    uint32_t* adMom;            // 3 planes of rows x width: m1, m2 (float bits), n (calls folded)
 };
 
 // Speculative sample groups: window of a group's start offset in which an earlier group's parse can

@@ -22,6 +22,7 @@
 //     hit record is reconstructed once for the closest hit instead of for every candidate hit.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 #include <rccl/rccl.h>
 #include <stdint.h>
 #include <cmath>
@@ -113,7 +114,10 @@ PT_DEV void run_item(const TraceParams& P, uint32_t slot, Counters& cnt)
     // call is done.  A wave leaves the tile as soon as no lane has samples of this launch left.  The
     // next launch continues from the stash when its camera and scene are the ones it was made with
     // (host key, render_impl); otherwise the stored state is the exact one to continue from.
-    constexpr bool SSG = MODE == 1, AUX = MODE == 2, STRIP = MODE == 3, AHEAD = MODE == 4;
+    // MODE 5 (ADAPT): adaptive sampling.  The wave's 64 pixels are entries of a compacted list of the
+    // active pixels (pixel_of_list); each runs `chunks` render() calls from its own stream and folds
+    // every call's luminance into its moments (end_call); no tile costs, no run-ahead stash.
+    constexpr bool SSG = MODE == 1, AUX = MODE == 2, STRIP = MODE == 3, AHEAD = MODE == 4, ADAPT = MODE == 5;
     // the call's colour sum in LDS (get_color): the plain six-wave launch only (measured there; the
     // run-ahead build was 0.9 % slower with it on the reference's call loop)
     constexpr bool CL = MINW >= 6 && MODE == 0;
@@ -139,7 +143,9 @@ PT_DEV void run_item(const TraceParams& P, uint32_t slot, Counters& cnt)
     else if (pos < P.prio[1]) __builtin_amdgcn_s_setprio(2);
     else if (pos < P.prio[2]) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
-    PixelCtx pc = pixel_of(P, tile, lane);
+    PixelCtx pc;
+    if constexpr (ADAPT) pc = pixel_of_list(P, slot, lane);
+    else pc = pixel_of(P, tile, lane);
     const uint64_t tWave = __builtin_amdgcn_s_memtime();
     const bool run = pc.valid && (!AUX || !P.fold || (P.fold[F_FLAG * pc.npix + pc.li] & 1u));
     if (run) {
@@ -194,7 +200,7 @@ PT_DEV void run_item(const TraceParams& P, uint32_t slot, Counters& cnt)
                 uint64_t tS = STATS ? __builtin_amdgcn_s_memtime() : 0;
                 if (shade<STATS>(P, prims, ts.elem, ts.tMax, ps, rng, cnt)) {
                     if (SSG) ssg_finish<STATS>(P, ps, rng, fx, fy, sl, lane, pc.li, cnt);
-                    else finish_path<STATS, AHEAD, CL>(P, ps, rng, fx, fy, cnt, pc);
+                    else finish_path<STATS, AHEAD, CL, ADAPT>(P, ps, rng, fx, fy, cnt, pc);
                     if (STRIP && !ps.alive && stripK + 1 < P.strip) {
                         // Strip units (launches of few samples per pixel): a lane whose pixel is done
                         // stores it and takes the same position in the unit's next tile -- the tile to
@@ -225,7 +231,7 @@ PT_DEV void run_item(const TraceParams& P, uint32_t slot, Counters& cnt)
             uint64_t tS = STATS ? __builtin_amdgcn_s_memtime() : 0;
             if (shade<STATS>(P, prims, e, t, ps, rng, cnt)) {
                 if (SSG) ssg_finish<STATS>(P, ps, rng, fx, fy, sl, lane, pc.li, cnt);
-                else finish_path<STATS, false, CL>(P, ps, rng, fx, fy, cnt, pc);
+                else finish_path<STATS, false, CL, ADAPT>(P, ps, rng, fx, fy, cnt, pc);
             }
             if (STATS) wave_time(cnt.cyc_shade, tS);
         }
@@ -245,7 +251,7 @@ PT_DEV void run_item(const TraceParams& P, uint32_t slot, Counters& cnt)
             P.pairsOut[pc.npix + pc.li] = -1.0f;      // odd-length fraction unknown
         }
     }
-    if (P.tileCost && lane == 0 && (tile >> 16) < P.tilesY) {
+    if (!ADAPT && P.tileCost && lane == 0 && (tile >> 16) < P.tilesY) {
         const uint32_t cyc = (uint32_t)min(__builtin_amdgcn_s_memtime() - tWave, (uint64_t)0xffffffffu);
         const uint32_t lin = (tile >> 16) * P.tilesX + (tile & 0xffffu);
         // SSG: zeroed before the launch (idle items add ~0)
@@ -270,7 +276,8 @@ PT_DEV void run_item(const TraceParams& P, uint32_t slot, Counters& cnt)
 // MODE 0: plain; 1 (SSG): speculative sample groups (ssg_load / ssg_finish), one work item per
 // (tile, group); 2: auxiliary launches -- the resume pass after a grouped launch, and the cost
 // pre-pass that also measures draw pairs per sample; 3: strip units; 4: run-ahead across render()
-// calls (run_item).  Separate instantiations keep the plain kernel's register allocation free of
+// calls (run_item); 5: adaptive sampling -- a wave's pixels are 64 entries of the compacted list of
+// active pixels, a slot is a wave of the list (pt_render_adaptive).  Separate instantiations keep the plain kernel's register allocation free of
 // their code.
 // First dispatch slot of wave `w` of workgroup `b` in a persistent grid of nCU x k workgroups.  The
 // hardware places workgroups 0..nCU-1 on distinct CUs (round robin over the XCDs) and a workgroup's
@@ -337,12 +344,9 @@ __global__ void __launch_bounds__(256) init_rng_kernel(uint32_t* rng, uint32_t w
     rng[5 * npix + li] = s.v4;
 }
 
-// tonemap (tonemap.cu:4-27)
-__global__ void __launch_bounds__(256) tonemap_kernel(uchar4* out, const float4* accum, size_t npix, uint32_t frames)
+// tonemap (tonemap.cu:4-27) of one accumulation value over `frames` render() calls
+PT_DEV uchar4 tonemap_pixel(const float4 a, uint32_t frames)
 {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    const float4 a = accum[i];
     f3 c = divs(mk(a.x, a.y, a.z), (float)frames);
     c = mul(mk(1.0f / (c.x + 1.0f), 1.0f / (c.y + 1.0f), 1.0f / (c.z + 1.0f)), c);
     const float g = 1.0f / 2.2f;
@@ -354,7 +358,98 @@ __global__ void __launch_bounds__(256) tonemap_kernel(uchar4* out, const float4*
         const int32_t v = (f != f) ? 0 : f2i_x86(f);
         q[k] = (unsigned char)(v & 0xff);
     }
-    out[i] = make_uchar4(q[0], q[1], q[2], 255);
+    return make_uchar4(q[0], q[1], q[2], 255);
+}
+
+__global__ void __launch_bounds__(256) tonemap_kernel(uchar4* out, const float4* accum, size_t npix, uint32_t frames)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    out[i] = tonemap_pixel(accum[i], frames);
+}
+
+// The same over an adaptive render's buffer: every pixel divided by its own number of calls.
+__global__ void __launch_bounds__(256) tonemap_adaptive_kernel(uchar4* out, const float4* accum, const uint32_t* calls,
+                                                               size_t npix)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    out[i] = tonemap_pixel(accum[i], calls[i]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Adaptive sampling (pt_render_adaptive): after every round each pixel is re-evaluated from its
+// moments and the active pixels are compacted into the list the next MODE 5 launch runs.
+// ---------------------------------------------------------------------------------------------
+// Pass 1: flag = the pixel has its minimum of calls and is not converged.  Batch-means standard
+// error of the per-call luminance against tolerance x (|mean| + floor); the float operations and
+// their order are the contract (tests/test_adaptive_rule.py restates them in numpy).  tolerance 0
+// never converges; a non-finite pixel (the reference's 0/0 pdf NaNs) counts as converged.
+__global__ void __launch_bounds__(256) adapt_flag_kernel(const uint32_t* __restrict__ mom, uint8_t* __restrict__ flag,
+                                                         size_t npix, float tolerance, float floorv, uint32_t minCalls)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const float m1 = __uint_as_float(mom[i]), m2 = __uint_as_float(mom[npix + i]);
+    const uint32_t n = mom[2 * npix + i];
+    const float k = (float)n;
+    const float mean = m1 / k;
+    float ss = m2 - m1 * mean;
+    if (ss < 0.0f) ss = 0.0f;
+    const float se2 = ss / (k * (k - 1.0f));
+    const float t = tolerance * (fabsf(mean) + floorv);
+    const bool conv = tolerance > 0.0f && ((se2 <= t * t) || !__builtin_isfinite(m2));
+    flag[i] = (n >= minCalls && !conv) ? 1u : 0u;
+}
+
+// Pass 2, one wave per 8x8 tile: a pixel is active below its minimum of calls, or below its maximum
+// when any pixel of its 3x3 neighbourhood (clipped to the context's rows and width) is flagged -- a
+// zero-variance dark pixel next to a noisy one keeps sampling.  `all`: every pixel (the first launch
+// of a reset render).  The tile's ballot and its popcount feed the scan and the scatter.
+__global__ void __launch_bounds__(256) adapt_mark_kernel(const uint8_t* __restrict__ flag, const uint32_t* __restrict__ calls,
+                                                         uint32_t width, uint32_t rows, uint32_t tilesX, uint32_t tiles,
+                                                         uint32_t minCalls, uint32_t maxCalls, uint32_t all,
+                                                         unsigned long long* __restrict__ masks, uint32_t* __restrict__ counts)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (tile >= tiles) return;
+    const uint32_t ty = tile / tilesX, tx = tile - ty * tilesX;
+    const uint32_t x = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);
+    bool active = false;
+    if (x < width && ly < rows) {
+        const size_t li = (size_t)ly * width + x;
+        const uint32_t n = all ? 0u : calls[li];
+        if (all || n < minCalls) active = true;
+        else if (n < maxCalls) {
+            const uint32_t y0 = ly > 0u ? ly - 1u : 0u, y1 = ly + 1u < rows ? ly + 1u : rows - 1u;
+            const uint32_t x0 = x > 0u ? x - 1u : 0u, x1 = x + 1u < width ? x + 1u : width - 1u;
+            for (uint32_t yy = y0; yy <= y1; ++yy)
+                for (uint32_t xx = x0; xx <= x1; ++xx) active = active || flag[(size_t)yy * width + xx] != 0u;
+        }
+    }
+    const unsigned long long m = __ballot(active);
+    if (lane == 0) {
+        masks[tile] = m;
+        counts[tile] = (uint32_t)__popcll(m);
+    }
+}
+
+// Scatter, one wave per tile: the tile's active pixels go to list[offset of the tile + the lane's rank
+// inside the ballot], so the list is tile-major and a wave of the next launch holds neighbouring pixels.
+__global__ void __launch_bounds__(256) adapt_scatter_kernel(const unsigned long long* __restrict__ masks,
+                                                            const uint32_t* __restrict__ offsets, uint32_t* __restrict__ list,
+                                                            uint32_t width, uint32_t tilesX, uint32_t tiles)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (tile >= tiles) return;
+    const unsigned long long m = masks[tile];
+    if (!((m >> lane) & 1ull)) return;
+    const uint32_t ty = tile / tilesX, tx = tile - ty * tilesX;
+    const uint32_t x = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);
+    const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    list[offsets[tile] + rank] = ly * width + x;
 }
 
 #include "pt_dev_fold.h"
@@ -460,6 +555,17 @@ struct pt_context {
     uint32_t lastGroups = 0;      // groups of the last launch (0 = plain launch)
     int lastVariant = 0;          // trace-kernel variant of the last launch's main pass
     uint32_t groupStats[10] = {}; // G, patch rounds, dead-end pixels after fold rounds 0..7
+    // adaptive sampling (pt_render_adaptive): per-pixel moments and the compaction buffers
+    uint32_t* adMom = nullptr;        // [3][pixels]: m1, m2 (float bits), n
+    bool adMomValid = false;          // the moments describe the accumulation buffer
+    uint32_t adSteps = 0;             // steps (calls of the active pixels) made since the last reset
+    uint8_t* adFlag = nullptr;        // [pixels] has its minimum of calls and is not converged
+    unsigned long long* adMasks = nullptr;   // [tiles] ballot of the tile's active pixels
+    uint32_t* adCounts = nullptr;     // [tiles + 1] their popcounts (the last entry stays 0)
+    uint32_t* adOffsets = nullptr;    // [tiles + 1] exclusive scan; the last entry is the active count
+    uint32_t* adList = nullptr;       // [pixels] active local pixel indices, tile-major
+    void* adTemp = nullptr;
+    size_t adTempBytes = 0;
     pt_camera lastCam = {};
     uint64_t epoch = 0;           // launches that wrote the accumulation (a group's gather cache key)
     std::string err;
@@ -546,7 +652,17 @@ static hipError_t launch_one(const TraceParams& P, hipStream_t stream)
             cap = cus * std::min(cap / cus, (int)P.occCap);
         else if (P.occCap)
             cap = 0;
-        if (!P.occCap && blocks <= (unsigned)cap) return launch_one<STATS, SL, WPB, WW, MINW, false, MODE>(P, stream);
+        if constexpr (MODE == 5) {
+            // adaptive rounds shrink from launch to launch: a list that fits in one pass runs the same
+            // kernel on a grid of its own size, every wave taking its slot from the cursor (one build
+            // per variant instead of two)
+            if (!P.occCap && blocks <= (unsigned)cap) {
+                trace_kernel<STATS, SL, WPB, WW, MINW, PERSIST, MODE><<<blocks, WPB * 64, lds, stream>>>(P);
+                return hipGetLastError();
+            }
+        } else {
+            if (!P.occCap && blocks <= (unsigned)cap) return launch_one<STATS, SL, WPB, WW, MINW, false, MODE>(P, stream);
+        }
         if (cap <= 0) return hipErrorInvalidValue;
         TraceParams Q = P;                             // first slots dealt per SIMD (spread_slot)
         Q.spreadCU = (cus > 0 && WPB % 4 == 0 && cap % cus == 0) ? (uint32_t)cus : 0u;
@@ -662,6 +778,24 @@ static hipError_t launch_ahead(int v, const TraceParams& P, hipStream_t stream)
     default: return hipErrorInvalidValue;
     }
 }
+
+// Adaptive-sampling launches (MODE 5): every variant pick_variant returns by itself -- the resumable
+// persistent walks and the node-at-a-time fallbacks.
+static hipError_t launch_adaptive(int v, const TraceParams& P, hipStream_t stream)
+{
+    switch (v) {
+    case 4: return launch_one<false, 0, 4, 1, 5, false, 5>(P, stream);
+    case 6: return launch_one<false, 1, 4, 1, 5, false, 5>(P, stream);
+    case 40: return launch_one<false, 1, 4, kV40Walk, 5, true, 5>(P, stream);
+    case 41: return launch_one<false, 0, 4, 14212, 5, true, 5>(P, stream);
+    case 46: return launch_one<false, 0, 4, 14212, 4, true, 5>(P, stream);
+    case 60: return launch_one<false, 1, 8, kV40Walk, 6, true, 5>(P, stream);
+    case 61: return launch_one<false, 0, 4, 14212, 6, true, 5>(P, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+static bool adaptive_capable(int v) { return v == 4 || v == 6 || strip_capable(v); }
 
 // Tiles per dispatch unit.  A launch of few samples per pixel idles the lanes whose pixels finish
 // first for the rest of their tile; strips of K tiles let those lanes go on with the next tile.
@@ -869,6 +1003,13 @@ PT_API void pt_destroy(pt_context* ctx)
     (void)hipFree(ctx->patchEnd);
     (void)hipFree(ctx->patchCount);
     (void)hipFree(ctx->ahead);
+    (void)hipFree(ctx->adMom);
+    (void)hipFree(ctx->adFlag);
+    (void)hipFree(ctx->adMasks);
+    (void)hipFree(ctx->adCounts);
+    (void)hipFree(ctx->adOffsets);
+    (void)hipFree(ctx->adList);
+    (void)hipFree(ctx->adTemp);
     for (auto& t : ctx->hostTex) (void)hipFree((void*)t.texels);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -1010,6 +1151,7 @@ PT_API int pt_set_scene(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node
     }
     ctx->dfsOrder = dfsOrder;
     ctx->orderStale = true;
+    ctx->adMomValid = false;
     ++ctx->stateEpoch;
     ctx->rootWord = word(0);
     for (int k = 0; k < 3; ++k) {
@@ -1069,6 +1211,7 @@ PT_API int pt_set_texture(pt_context* ctx, uint32_t handle, const float* rgba, u
     t.fwidth = (float)width;
     t.fheight = (float)height;
     ctx->orderStale = true;
+    ctx->adMomValid = false;
     ++ctx->stateEpoch;
     PT_HIP_CHECK(ctx, hipMemcpy(ctx->texTable, ctx->hostTex, sizeof(ctx->hostTex), hipMemcpyHostToDevice));
     return PT_OK;
@@ -1078,7 +1221,10 @@ PT_API int pt_set_skybox(pt_context* ctx, uint32_t handle)
 {
     if (!ctx) return PT_ERR_ARG;
     if (handle > PT_MAX_TEXTURES) return fail(ctx, PT_ERR_ARG, "pt_set_skybox: invalid handle");
-    if (ctx->skybox != handle) ++ctx->stateEpoch;
+    if (ctx->skybox != handle) {
+        ++ctx->stateEpoch;
+        ctx->adMomValid = false;
+    }
     ctx->skybox = handle;
     return PT_OK;
 }
@@ -1304,18 +1450,10 @@ static void issue_priority(const pt_context* ctx, uint32_t tiles, uint32_t* prio
     prio[2] = tiles - tiles / 4;
 }
 
-static int render_impl(pt_context* ctx, const pt_camera* cam, uint32_t spp, uint32_t chunks, int ignore, float* gpu_ms,
-                       pt_render_stats* stats)
+// The launch parameters every trace launch of the context shares: buffers, scene, image, camera.
+static void base_params(const pt_context* ctx, const pt_camera* cam, uint32_t spp, uint32_t chunks, int ignore,
+                        TraceParams& P)
 {
-    if (!ctx || !cam) return PT_ERR_ARG;
-    if (gpu_ms) *gpu_ms = 0.0f;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (ctx->nodeCount < 1 || ctx->primCount < 1 || spp == 0 || chunks == 0 || ctx->rows == 0) return PT_OK;
-    // textures referenced by the launch must exist (the reference would read an invalid object)
-    if (ctx->skybox != 0 && ctx->hostTex[ctx->skybox - 1].texels == nullptr)
-        return fail(ctx, PT_ERR_STATE, "pt_render: skybox handle has no texture");
-    TraceParams P;
     memset(&P, 0, sizeof(P));
     P.accum = ctx->accum;
     P.rng = ctx->rng;
@@ -1351,6 +1489,22 @@ static int render_impl(pt_context* ctx, const pt_camera* cam, uint32_t spp, uint
     P.cnodeCount = ctx->cnodeCount;
     P.rootWord = ctx->rootWord;
     for (int k = 0; k < 6; ++k) P.rootBox[k] = ctx->rootBox[k];
+}
+
+static int render_impl(pt_context* ctx, const pt_camera* cam, uint32_t spp, uint32_t chunks, int ignore, float* gpu_ms,
+                       pt_render_stats* stats)
+{
+    if (!ctx || !cam) return PT_ERR_ARG;
+    if (gpu_ms) *gpu_ms = 0.0f;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (ctx->nodeCount < 1 || ctx->primCount < 1 || spp == 0 || chunks == 0 || ctx->rows == 0) return PT_OK;
+    // textures referenced by the launch must exist (the reference would read an invalid object)
+    if (ctx->skybox != 0 && ctx->hostTex[ctx->skybox - 1].texels == nullptr)
+        return fail(ctx, PT_ERR_STATE, "pt_render: skybox handle has no texture");
+    TraceParams P;
+    base_params(ctx, cam, spp, chunks, ignore, P);
+    ctx->adMomValid = false;              // the moments of an adaptive render no longer describe the buffer
     // Tile scheduling: a pixel's samples are sequential (one XORWOW stream), so a tile is the
     // smallest unit of work, and tiles differ several-fold in cost (sky vs geometry).  Every
     // launch records each tile's cycle count; after a scene, texture or camera change the
@@ -1792,6 +1946,183 @@ PT_API int pt_render_instrumented(pt_context* ctx, const pt_camera* camera, uint
     return render_impl(ctx, camera, spp, chunks, ignore_history, gpu_ms, stats);
 }
 
+// Buffers of the adaptive path, allocated by the first adaptive render of the context.
+static int adaptive_reserve(pt_context* ctx, uint32_t tiles)
+{
+    if (ctx->adMom) return PT_OK;
+    const size_t npix = (size_t)ctx->rows * ctx->width;
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->adMom, 3 * npix * sizeof(uint32_t)));
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->adFlag, npix));
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->adList, npix * sizeof(uint32_t)));
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->adMasks, (size_t)tiles * sizeof(unsigned long long)));
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->adCounts, ((size_t)tiles + 1) * sizeof(uint32_t)));
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->adOffsets, ((size_t)tiles + 1) * sizeof(uint32_t)));
+    PT_HIP_CHECK(ctx, hipMemsetAsync(ctx->adCounts, 0, ((size_t)tiles + 1) * sizeof(uint32_t), ctx->stream));
+    ctx->adTempBytes = 0;
+    PT_HIP_CHECK(ctx, rocprim::exclusive_scan(nullptr, ctx->adTempBytes, ctx->adCounts, ctx->adOffsets, 0u, (size_t)tiles + 1,
+                                              rocprim::plus<uint32_t>(), ctx->stream));
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->adTemp, ctx->adTempBytes ? ctx->adTempBytes : 4));
+    return PT_OK;
+}
+
+// Evaluate every pixel and compact the active ones into ctx->adList; the count is the one readback.
+static int adaptive_compact(pt_context* ctx, const pt_adaptive_params& ap, bool all, uint32_t tilesX, uint32_t tiles,
+                            uint32_t* count)
+{
+    const size_t npix = (size_t)ctx->rows * ctx->width;
+    hipStream_t s = ctx->stream;
+    if (!all) {
+        adapt_flag_kernel<<<(unsigned)((npix + 255) / 256), 256, 0, s>>>(ctx->adMom, ctx->adFlag, npix, ap.tolerance, ap.floor,
+                                                                         ap.min_calls);
+        PT_HIP_CHECK(ctx, hipGetLastError());
+    }
+    const unsigned tileBlocks = (tiles + 3) / 4;
+    adapt_mark_kernel<<<tileBlocks, 256, 0, s>>>(ctx->adFlag, ctx->adMom + 2 * npix, ctx->width, ctx->rows, tilesX, tiles,
+                                                 ap.min_calls, ap.max_calls, all ? 1u : 0u, ctx->adMasks, ctx->adCounts);
+    PT_HIP_CHECK(ctx, hipGetLastError());
+    size_t bytes = ctx->adTempBytes;
+    PT_HIP_CHECK(ctx, rocprim::exclusive_scan(ctx->adTemp, bytes, ctx->adCounts, ctx->adOffsets, 0u, (size_t)tiles + 1,
+                                              rocprim::plus<uint32_t>(), s));
+    adapt_scatter_kernel<<<tileBlocks, 256, 0, s>>>(ctx->adMasks, ctx->adOffsets, ctx->adList, ctx->width, tilesX, tiles);
+    PT_HIP_CHECK(ctx, hipGetLastError());
+    PT_HIP_CHECK(ctx, hipMemcpyAsync(count, ctx->adOffsets + tiles, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    PT_HIP_CHECK(ctx, hipStreamSynchronize(s));
+    return PT_OK;
+}
+
+PT_API int pt_render_adaptive(pt_context* ctx, const pt_camera* camera, const pt_adaptive_params* params,
+                              pt_adaptive_result* result)
+{
+    if (!ctx) return PT_ERR_ARG;
+    if (result) memset(result, 0, sizeof(*result));
+    if (!camera || !params) return fail(ctx, PT_ERR_ARG, "pt_render_adaptive: null argument");
+    const pt_adaptive_params ap = *params;
+    if (ap.spp == 0 || ap.min_calls < 2 || ap.max_calls < ap.min_calls || !(ap.tolerance >= 0.0f) || !(ap.floor >= 0.0f))
+        return fail(ctx, PT_ERR_ARG, "pt_render_adaptive: needs spp >= 1, 2 <= min_calls <= max_calls, tolerance >= 0, floor >= 0");
+    PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (ctx->nodeCount < 1 || ctx->primCount < 1) return fail(ctx, PT_ERR_STATE, "pt_render_adaptive: no scene set");
+    if (ctx->skybox != 0 && ctx->hostTex[ctx->skybox - 1].texels == nullptr)
+        return fail(ctx, PT_ERR_STATE, "pt_render_adaptive: skybox handle has no texture");
+    if (!ap.reset && !ctx->adMomValid)
+        return fail(ctx, PT_ERR_STATE, "pt_render_adaptive: reset = 0 needs the moments of an adaptive render; there has been "
+                                       "none since the last plain render, RNG write or scene, texture or sky change");
+    const int variant = pick_variant(ctx);
+    if (!adaptive_capable(variant))
+        return fail(ctx, PT_ERR_ARG, "pt_render_adaptive: the kernel variant set has no adaptive build (0, 4, 6, 40, 41, 46, 60, 61 have)");
+    if (ctx->rows == 0) return PT_OK;
+    const uint32_t tilesX = (ctx->width + 7) / 8, tiles = tilesX * ((ctx->rows + 7) / 8);
+    const int rr = adaptive_reserve(ctx, tiles);
+    if (rr != PT_OK) return rr;
+    if (!ctx->tileCursor) {
+        PT_HIP_CHECK(ctx, hipMalloc(&ctx->tileCursor, 2 * sizeof(uint32_t)));
+        PT_HIP_CHECK(ctx, hipMemset(ctx->tileCursor, 0, 2 * sizeof(uint32_t)));
+    }
+    TraceParams P;
+    base_params(ctx, camera, ap.spp, 1, 0, P);
+    P.tileCursor = ctx->tileCursor;
+    P.occCap = ctx->occupancy;
+    P.adList = ctx->adList;
+    P.adMom = ctx->adMom;
+    // the accumulation and the RNG streams move on: a run-ahead stash of the old state is void; the
+    // cost order and the tile costs stay as they were (this path dispatches no tiles)
+    ctx->aheadValid = false;
+    ++ctx->stateEpoch;
+    ++ctx->epoch;
+    ctx->adMomValid = false;              // until the render is complete
+    ctx->lastGroups = 0;
+    ctx->lastVariant = variant;
+    PT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    uint32_t rounds = 0, count = 0;
+    uint64_t samples = 0;
+    if (ap.reset) {
+        // every pixel is active for its first min_calls calls: one fused launch, the first call
+        // overwriting the accumulation value (ignoreHistory) and starting from zero moments
+        const int rc = adaptive_compact(ctx, ap, true, tilesX, tiles, &count);
+        if (rc != PT_OK) return rc;
+        P.adCount = count;
+        P.numSlots = (count + 63) / 64;
+        P.chunks = ap.min_calls;
+        P.ignoreFirst = 1;
+        PT_HIP_CHECK(ctx, launch_adaptive(variant, P, ctx->stream));
+        rounds = 1;
+        ctx->adSteps = ap.min_calls;
+        samples = (uint64_t)count * ap.min_calls * ap.spp;
+        P.chunks = 1;
+        P.ignoreFirst = 0;
+    }
+    // one step per launch, at most max_calls steps since the reset: a pixel that stopped and started
+    // again ends below max_calls, and the render's length is bounded by its budget
+    while (ctx->adSteps < ap.max_calls) {
+        const int rc = adaptive_compact(ctx, ap, false, tilesX, tiles, &count);
+        if (rc != PT_OK) return rc;
+        if (count == 0) break;            // nothing active: no launch
+        P.adCount = count;
+        P.numSlots = (count + 63) / 64;
+        PT_HIP_CHECK(ctx, launch_adaptive(variant, P, ctx->stream));
+        ++rounds;
+        ++ctx->adSteps;
+        samples += (uint64_t)count * ap.spp;
+    }
+    PT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    PT_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
+    float ms = 0.0f;
+    PT_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->adMomValid = true;
+    if (result) {
+        result->rounds = rounds;
+        result->samples = samples;
+        result->gpu_ms = ms;
+    }
+    return PT_OK;
+}
+
+PT_API int pt_read_moments(pt_context* ctx, float* dst)
+{
+    if (!ctx || !dst) return PT_ERR_ARG;
+    if (!ctx->adMomValid) return fail(ctx, PT_ERR_STATE, "pt_read_moments: no adaptive render describes the buffer");
+    PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t npix = (size_t)ctx->rows * ctx->width;
+    std::vector<uint32_t> soa(3 * npix);
+    PT_HIP_CHECK(ctx, hipMemcpy(soa.data(), ctx->adMom, soa.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < npix; ++i)
+        for (int k = 0; k < 3; ++k) dst[3 * i + k] = u2f(soa[k * npix + i]);
+    return PT_OK;
+}
+
+PT_API int pt_read_adaptive_hdr(pt_context* ctx, float* dst)
+{
+    if (!ctx || !dst) return PT_ERR_ARG;
+    if (!ctx->adMomValid) return fail(ctx, PT_ERR_STATE, "pt_read_adaptive_hdr: no adaptive render describes the buffer");
+    PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t npix = (size_t)ctx->rows * ctx->width;
+    std::vector<uint32_t> calls(npix);
+    PT_HIP_CHECK(ctx, hipMemcpy(dst, ctx->accum, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    PT_HIP_CHECK(ctx, hipMemcpy(calls.data(), ctx->adMom + 2 * npix, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < npix; ++i) {
+        const float n = (float)std::max(calls[i], 1u);
+        for (int k = 0; k < 4; ++k) dst[4 * i + k] = dst[4 * i + k] / n;
+    }
+    return PT_OK;
+}
+
+PT_API int pt_tonemap_adaptive(pt_context* ctx, uint8_t* dst)
+{
+    if (!ctx || !dst) return PT_ERR_ARG;
+    if (!ctx->adMomValid) return fail(ctx, PT_ERR_STATE, "pt_tonemap_adaptive: no adaptive render describes the buffer");
+    PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const size_t npix = (size_t)ctx->rows * ctx->width;
+    if (npix == 0) return PT_OK;
+    if (!ctx->ldr) PT_HIP_CHECK(ctx, hipMalloc(&ctx->ldr, npix * sizeof(uchar4)));
+    tonemap_adaptive_kernel<<<(unsigned)((npix + 255) / 256), 256, 0, ctx->stream>>>(ctx->ldr, ctx->accum,
+                                                                                      ctx->adMom + 2 * npix, npix);
+    PT_HIP_CHECK(ctx, hipGetLastError());
+    PT_HIP_CHECK(ctx, hipMemcpyAsync(dst, ctx->ldr, npix * sizeof(uchar4), hipMemcpyDeviceToHost, ctx->stream));
+    PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return PT_OK;
+}
+
 PT_API int pt_read_accum(pt_context* ctx, float* dst)
 {
     if (!ctx || !dst) return PT_ERR_ARG;
@@ -1864,6 +2195,7 @@ PT_API int pt_write_rng(pt_context* ctx, const uint32_t* src)
         for (int k = 0; k < 6; ++k) soa[k * npix + i] = src[6 * i + k];
     PT_HIP_CHECK(ctx, hipMemcpy(ctx->rng, soa.data(), soa.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     ++ctx->stateEpoch;                    // a run-ahead stash continues the old streams: void
+    ctx->adMomValid = false;
     return PT_OK;
 }
 
