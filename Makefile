@@ -5,6 +5,8 @@
 #   pathtracercuda_amd/lib/fp_exhaustive  all-inputs check of the kernel's fast 1/x and sqrt (GPU)
 #   pathtracercuda_amd/lib/host_sanitize_check  ASan/UBSan mutation check of the host parsers (CPU)
 #   oracle/liboracle.so                   CPU restatement (test infrastructure only)
+#   oracle/_ref/libptref.so               the reference's own source built for the host, when a checkout
+#                                         of it is at $(REF) (test infrastructure only; oracle/Makefile)
 # Every FP unit is built with -ffp-contract=off: the GPU result is compared bit for bit with the
 # oracle, and the host-built BVH / transforms / camera feed the GPU directly.
 HIPCC ?= /opt/rocm/bin/hipcc
@@ -12,6 +14,7 @@ CXX ?= g++
 ARCH ?= gfx950
 LIB := pathtracercuda_amd/lib
 SRC := pathtracercuda_amd/csrc
+REF ?= $(abspath ../reference)
 HOST_SRCS := $(SRC)/host/math_camera.cpp $(SRC)/host/hittable.cpp $(SRC)/host/bvh_build.cpp \
              $(SRC)/host/json_min.cpp $(SRC)/host/scene_json.cpp $(SRC)/host/image_io.cpp \
              $(SRC)/host/renderer.cpp $(SRC)/host/host_capi.cpp
@@ -44,7 +47,7 @@ $(LIB)/fp_exhaustive: tools/fp_exhaustive.hip $(SRC)/pt_math.h | $(LIB)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -o $@ tools/fp_exhaustive.hip
 
 oracle:
-	$(MAKE) -C oracle
+	$(MAKE) -C oracle REF=$(REF)
 
 # CPU-only sanitizer build of the host parsers (scene JSON, RGBE/PNG decode, BVH build) with a
 # mutation driver; run by tests/test_host.py.  Links libpt_hip.so for the symbols only (no GPU call).
@@ -58,8 +61,10 @@ sanitize: $(LIB)/host_sanitize_check
 clean:
 	rm -f $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer
 	$(MAKE) -C oracle clean
+clean-ref:
+	$(MAKE) -C oracle clean-ref
 
-.PHONY: all oracle clean sanitize
+.PHONY: all oracle clean clean-ref sanitize
 
 # `make -s print-HIPFLAGS`: the flags snapshot builds (tools/snap_rev.sh) reuse
 print-%:

@@ -9,8 +9,10 @@
  * -ffp-contract=off), so the HIP megakernel can be compared with it bit for bit.
  *
  * PARITY STATUS vs the original CUDA binary: UNPINNED.  The reference has no tests, golden vectors
- * or KATs; compiling/executing the reference's own sources in this container
- * was refused (binding).  Three third-party behaviours are restated, not pinned:
+ * or KATs, and its CUDA build was never run.  PARITY STATUS vs the reference's
+ * source: bit-exact with that source compiled for the host (ref_wrap.cpp over ref_shim/,
+ * tests/test_ref_source.py), which takes the exported or_xorwow_*, or_tex2d and pm_* of this file for
+ * what its tree does not contain.  Those three third-party behaviours are restated, not pinned:
  *   - cuRAND XORWOW (curand_init / curand_uniform, CUDA 10.2);
  *   - CUDA libdevice acosf/atan2f/sinf/cosf/powf: replaced by the Cephes-style single-precision
  *     routines below (the HIP kernel implements the same routines);

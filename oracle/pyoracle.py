@@ -270,11 +270,50 @@ def _resolve(path: str, scene_dir: pathlib.Path) -> str:
     return str(alt) if alt.exists() else path
 
 
-def load_scene(path: os.PathLike, width: int, height: int) -> OracleScene:
+class SceneInputs:
+    """What SceneLoader.cpp hands to the constructors, narrowed to float32: per-object arrays (file
+    order, rotation already in radians), the decoded textures and the camera parameters.  Shared by
+    load_scene() below and oracle/pyref.py, so both build from the same values."""
+
+    def __init__(self) -> None:
+        self.types: List[int] = []
+        self.positions: List[list] = []
+        self.rotations: List[list] = []       # radians
+        self.scales: List[list] = []
+        self.material_types: List[int] = []
+        self.base_colors: List[list] = []
+        self.emissives: List[list] = []
+        self.roughness: List[float] = []
+        self.metalness: List[float] = []
+        self.texture_handles: List[int] = []
+        self.has_objects = False
+        self.textures: List[np.ndarray] = []
+        self.skybox = 0
+        self.camera_position = [0.0] * 3
+        self.camera_look_at = [0.0, 0.0, -1.0]
+        self.camera_fovy = 0.0                # radians
+
+    def __len__(self) -> int:
+        return len(self.types)
+
+    def load_texture(self, path: str) -> int:
+        """Pathtracer::loadTexture (Pathtracer.cpp:234-292): 0 on failure or when 64 are loaded."""
+        if len(self.textures) >= 64:
+            return 0
+        p = pathlib.Path(path)
+        try:
+            tex = read_rgbe(p) if is_hdr(p) else read_ldr(p)
+        except Exception:
+            return 0
+        self.textures.append(np.ascontiguousarray(tex, dtype=np.float32))
+        return len(self.textures)
+
+
+def parse_scene(path: os.PathLike) -> SceneInputs:
     L = lib()
     scene_path = pathlib.Path(path)
     j = json.loads(scene_path.read_text())
-    sc = OracleScene()
+    si = SceneInputs()
     handles = {}
 
     def tex_handle(p: str) -> int:
@@ -282,7 +321,7 @@ def load_scene(path: os.PathLike, width: int, height: int) -> OracleScene:
             return 0
         if p in handles:
             return handles[p]
-        h = sc.load_texture(_resolve(p, scene_path.parent))
+        h = si.load_texture(_resolve(p, scene_path.parent))
         handles[p] = h
         return h
 
@@ -300,7 +339,7 @@ def load_scene(path: os.PathLike, width: int, height: int) -> OracleScene:
 
     objs = j.get("objects")
     if isinstance(objs, list):
-        cpu = []
+        si.has_objects = True
         for o in objs:
             htype, pos, rot, scale = 0, [0.0] * 3, [0.0] * 3, [1.0] * 3
             mtype, base, emis, rough, metal, texh = 0, [1.0] * 3, [0.0] * 3, np.float32(0.5), np.float32(0.0), 0
@@ -328,25 +367,55 @@ def load_scene(path: os.PathLike, width: int, height: int) -> OracleScene:
                 tp = m.get("texture")
                 if isinstance(tp, str):
                     texh = tex_handle(tp)
-            mat = Material()
-            L.or_material_make(mtype, f3(base), f3(emis), float(rough), float(metal), texh, C.byref(mat))
-            rrad = [L.or_radians(float(x)) for x in rot]
-            h = CpuHittable()
-            L.or_cpu_hittable_make(htype, f3(pos), f3(rrad), f3(scale), C.byref(mat), C.byref(h))
-            cpu.append(h)
-        sc.cpu = cpu
-        sc.set_scene(cpu)
+            si.types.append(htype)
+            si.positions.append([float(x) for x in pos])
+            si.rotations.append([L.or_radians(float(x)) for x in rot])
+            si.scales.append([float(x) for x in scale])
+            si.material_types.append(mtype)
+            si.base_colors.append([float(x) for x in base])
+            si.emissives.append([float(x) for x in emis])
+            si.roughness.append(float(rough))
+            si.metalness.append(float(metal))
+            si.texture_handles.append(texh)
     sky = j.get("skybox")
     if isinstance(sky, str):
-        sc.skybox = tex_handle(sky)
+        si.skybox = tex_handle(sky)
     cpos, look, fovy = [0.0] * 3, [0.0, 0.0, -1.0], np.float32(60.0)
     c = j.get("camera")
     if isinstance(c, dict):
         cpos = get_vec3(c, "position", cpos)
         look = get_vec3(c, "look_at", look)
         fovy = get_float(c, "fovy", fovy)
-    aspect = float(np.float32(np.float32(width) / np.float32(height)))
-    L.or_camera_make(f3(cpos), f3(look), f3([0.0, 1.0, 0.0]), L.or_radians(float(fovy)), aspect, C.byref(sc.camera))
+    si.camera_position = [float(x) for x in cpos]
+    si.camera_look_at = [float(x) for x in look]
+    si.camera_fovy = L.or_radians(float(fovy))
+    return si
+
+
+def aspect_of(width: int, height: int) -> float:
+    return float(np.float32(np.float32(width) / np.float32(height)))
+
+
+def load_scene(path: os.PathLike, width: int, height: int) -> OracleScene:
+    L = lib()
+    si = parse_scene(path)
+    sc = OracleScene()
+    sc.textures = si.textures
+    if si.has_objects:
+        cpu = []
+        for i in range(len(si)):
+            mat = Material()
+            L.or_material_make(si.material_types[i], f3(si.base_colors[i]), f3(si.emissives[i]), si.roughness[i],
+                               si.metalness[i], si.texture_handles[i], C.byref(mat))
+            h = CpuHittable()
+            L.or_cpu_hittable_make(si.types[i], f3(si.positions[i]), f3(si.rotations[i]), f3(si.scales[i]),
+                                   C.byref(mat), C.byref(h))
+            cpu.append(h)
+        sc.cpu = cpu
+        sc.set_scene(cpu)
+    sc.skybox = si.skybox
+    L.or_camera_make(f3(si.camera_position), f3(si.camera_look_at), f3([0.0, 1.0, 0.0]), si.camera_fovy,
+                     aspect_of(width, height), C.byref(sc.camera))
     return sc
 
 
