@@ -147,7 +147,17 @@ PT_API void pt_destroy(pt_context *ctx);
 
 /* Pathtracer::setScene upload half (Pathtracer.cpp:137-159): nodes and primitives as produced by
  * the host BVH build (elements already reordered).  Replaces the previous scene.  Returns
- * PT_ERR_DEPTH if a traversal could overflow the reference's 32-entry stack. */
+ * PT_ERR_DEPTH if a traversal could overflow the reference's 32-entry stack.
+ * Checked: node and primitive indices, leaf ranges, split axes, the tree's shape and depth, the
+ * shape and material types and texture handles.
+ * Floats: every entry of a primitive's inv_transform_rows must be finite; PT_ERR_ARG otherwise, and
+ * the message names the primitive and the entry.  (A scale of 0, or below 2^-128 where 1 / scale
+ * overflows, produces such rows; the scene loader refuses it for the same reason, naming
+ * objects[i].scale.)  All other floats are taken as they are, and every finite float32 renders as
+ * the reference's source does (words equal, or both NaN: DESIGN.md 3.1): roughness of any value
+ * (the loader raises it to 0.04, a caller's smaller value is used as given), metalness outside
+ * [0, 1], negative and huge base colours and emission, mirrored scales, scales of 1e-6 to 1e6.
+ * NaN or infinite values elsewhere (a NaN roughness, a NaN box) are not refused and not tested. */
 PT_API int pt_set_scene(pt_context *ctx, const pt_bvh_node *nodes, uint32_t node_count, const pt_hittable *prims,
                         uint32_t prim_count);
 

@@ -1,5 +1,6 @@
 // Scene file loading (reference src/SceneLoader.cpp:124-348): JSON objects -> CpuHittable list,
 // textures (memoised by path, loaded in order of first use, skybox after the objects), camera.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -127,6 +128,22 @@ bool parseSceneFile(const std::string& path, SceneDesc& out, std::string& error,
             out.objects.push_back(CpuHittable(htype, position,
                                               vec3(radians(rotation.x), radians(rotation.y), radians(rotation.z)), scale,
                                               Material(mtype, baseColor, emissive, roughness, metalness, tex)));
+            // Refused, not rendered: a scale of 0 (or below 2^-128, where 1 / scale
+            // overflows) puts inf and NaN into the inverse transform, every hit distance of the object
+            // is NaN, and the default walk is not the reference's on such a scene.  (The y scale of a
+            // disk or quad is overridden by the constructor and may be anything.)
+            const pt_hittable g = out.objects.back().getGpuHittable();
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 4; ++c)
+                    if (!std::isfinite(g.inv_transform_rows[r][c])) {
+                        char buf[256];
+                        snprintf(buf, sizeof(buf),
+                                 "objects[%u].scale = (%g, %g, %g): the inverse transform is not finite; every scale "
+                                 "component the shape uses must be larger in magnitude than 2^-128 (2.94e-39)",
+                                 oi, scale.x, scale.y, scale.z);
+                        error = buf;
+                        return false;
+                    }
         }
     }
     std::string sky;

@@ -117,10 +117,13 @@ PT_DEV float vndf_pdf(f3 H, f3 V, float a)    // MonteCarlo.h:104-114
 PT_DEV f3 specular_ggx(f3 F0, float NdotV, float NdotL, float NdotH, float VdotH, float a2)  // brdf.h:56-62
 {
     const float D = d_ggx(NdotH, a2);
-    // brdf.h:18-24.  NdotV = |V.z| + 1e-5, so the first operand, NdotV^2 (1 - a2) + a2 with a2 in
-    // [0, 1], is NaN or >= 1e-10 (sqrt_dom); NdotL may be any value in [0, 1], so the second keeps
-    // the guarded root
-    const float sv = sqrt_dom((-NdotV * a2 + NdotV) * NdotV + a2);
+    // brdf.h:18-24.  NdotV = |V.z| + 1e-5 lies in [1e-5, 1 + 1e-5] and a2 = roughness^4 is any value
+    // >= 0, +inf included (nothing bounds roughness from above).  The first operand, NdotV^2 (1 - a2)
+    // + a2, is then NaN (a2 = inf), at least 1e-10 (a2 <= 1), or, for a2 > 1, a multiple of ulp(a2) / 2
+    // >= 2^-24 of either sign or +0 (never -0: a2 is added last and is not -0).  It is negative for
+    // a2 > ~50001 (roughness > 14.95) near normal incidence, where the reference's sqrtf gives NaN:
+    // sqrt_dom_neg.  NdotL may be any value in [0, 1], so the second keeps the guarded root
+    const float sv = sqrt_dom_neg((-NdotV * a2 + NdotV) * NdotV + a2);
     const float sl = sqrt_rn((-NdotL * a2 + NdotL) * NdotL + a2);
     const float lv = NdotL * sv;
     const float ll = NdotV * sl;

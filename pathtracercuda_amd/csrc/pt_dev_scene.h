@@ -357,7 +357,10 @@ PT_DEV void wave_tick(uint32_t& c)
 // lane l is stack[64 * k], so one wave-wide push/pop touches 64 distinct banks-pairs, conflict-free).
 // Slab test of node `cur` against the ray's running interval (AABB.inl:22-44).  The reference
 // recomputes 1/d per node and axis, a function of the ray only, so it is hoisted (bit-identical);
-// the early returns are dropped because both bounds are monotone and never NaN.  Device node
+// the early returns are dropped because both bounds are monotone; the lower one is never NaN, and the
+// upper one is NaN exactly when the ray's t_max is (a NaN hit distance passes every range test of
+// prim_hit_rec and becomes t_max, e.g. from a primitive of zero scale or a NaN ray): then no
+// `tMax <= tMin` of the reference is true and every box is hit, hence `!(hi <= lo)`.  Device node
 // layout (pt_set_scene): A = (min.x, max.x, min.y, max.y), B = (min.z, max.z, offset, pca).
 struct NodeHit {
     bool hit;
@@ -389,11 +392,23 @@ PT_DEV NodeHit node_test(const float4* __restrict__ nodes, uint32_t cur, f3 o, f
         lo = t0 > lo ? t0 : lo;
         hi = t1 < hi ? t1 : hi;
     }
-    return NodeHit{hi > lo, __float_as_uint(Bq.z), __float_as_uint(Bq.w)};
+    return NodeHit{!(hi <= lo), __float_as_uint(Bq.z), __float_as_uint(Bq.w)};
 }
 
-// Fast form, exact when 1/d is finite on all axes and the box is not inverted (checked per ray
-// and per scene): then no product is NaN, the swap on a negative 1/d is min/max of the two slab
+// The per-ray half of the fast form's condition.  The origin counts too: after a hit at a NaN distance
+// the next ray starts at a NaN point, often in a finite direction (a cosine sample about a flat shape's
+// normal), and the exact form's selects skip its NaN products where v_min3/v_max3 would hand one on.
+// One sum stands for the three components: it is finite only if all are (an overflowing or cancelling
+// sum of finite ones only sends the ray to the exact form).
+PT_DEV bool slab_fast_ray(bool slabFast, f3 o, float ix, float iy, float iz)
+{
+    return slabFast && __builtin_isfinite(ix) && __builtin_isfinite(iy) && __builtin_isfinite(iz) &&
+           __builtin_isfinite((o.x + o.y) + o.z);
+}
+
+// Fast form, exact when the ray's origin and 1/d are finite on all axes, the box is not inverted (checked per ray
+// and per scene) and t_max is not NaN (v_min3 would drop it; the walk leaves the fast form when a hit
+// distance is NaN): then no product is NaN, the swap on a negative 1/d is min/max of the two slab
 // distances, and the running max/min over the axes is order-independent, so v_max3/v_min3 and
 // packed subtract/multiply give the reference's values.
 PT_DEV NodeHit node_test_fast(const float4* __restrict__ nodes, uint32_t cur, f2v ox2, f2v oy2, f2v oz2, f2v ix2,
@@ -430,7 +445,7 @@ PT_DEV uint32_t traverse(const float4* __restrict__ nodes, const float4* __restr
     const float ix = rcp_rn(d.x), iy = rcp_rn(d.y), iz = rcp_rn(d.z);
     // trace.cu:31-36: dirIsNeg from 1/(d != 0 ? d : 1e-7) < 0, i.e. d < 0
     const uint32_t negMask = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
-    const bool fast = slabFast && __builtin_isfinite(ix) && __builtin_isfinite(iy) && __builtin_isfinite(iz);
+    bool fast = slab_fast_ray(slabFast, o, ix, iy, iz);
     const f2v ox2 = f2(o.x, o.x), oy2 = f2(o.y, o.y), oz2 = f2(o.z, o.z);
     const f2v ix2 = f2(ix, ix), iy2 = f2(iy, iy), iz2 = f2(iz, iz);
     auto test = [&](uint32_t node) {
@@ -451,6 +466,7 @@ PT_DEV uint32_t traverse(const float4* __restrict__ nodes, const float4* __restr
                         if (prim_hit(prims, nh.offset + i, o, d, tMin, tMax, t)) {
                             tMax = t;
                             elem = nh.offset + i;
+                            fast = fast && t == t;                 // a NaN t_max: the exact slab test
                         }
                     }
                     if (sp == 0) break;
@@ -498,6 +514,7 @@ PT_DEV uint32_t traverse(const float4* __restrict__ nodes, const float4* __restr
                 if (prim_hit(prims, leafOff, o, d, tMin, tMax, t)) {
                     tMax = t;
                     elem = leafOff;
+                    fast = fast && t == t;                         // a NaN t_max: the exact slab test
                 }
                 ++leafOff;
                 --leafCnt;

@@ -57,6 +57,33 @@ PT_DEV float slab_lo_x(const SlabRay& R, f2v bx, f2v by, f2v bz, float tMin, flo
     return lo;
 }
 
+// A NaN t_max -- a NaN hit distance passes every range test of prim_hit_rec, e.g. from a primitive
+// of zero scale or a NaN ray -- passes every box test of the reference (AABB.inl:36-41: the upper
+// bound stays NaN and no `tMax <= tMin` is true), also of boxes the ray misses.  The child-box walks
+// get that from the slab test itself: with NaN reciprocals every product is NaN, the selects of the
+// exact form keep lo = t_min and X = +inf, and the re-test `!(tMax <= lo)` holds.  In the one-pass walk
+// (traverse_cb) the lane that finds its t_max NaN after a leaf switches its ray to this form and
+// rebuilds its pending set (repair_pending then keeps every far child), like a lane whose t_max rose.
+// A later hit can replace the NaN by a number (`t > tMax` is false for it too): the lane takes its
+// ray's own reciprocals back (slab_restore; 1 / x is rcp_rn's value) and rebuilds again.  The
+// resumable walk (traverse_cb_phase) takes the form only when a phase resumes: see its leaf branch.
+PT_DEV void slab_pass_all(SlabRay& R)
+{
+    R.ix = R.iy = R.iz = __uint_as_float(0x7fc00000u);
+    R.fast = false;
+}
+
+PT_DEV void slab_restore(SlabRay& R, f3 d, bool slabFast)
+{
+    R.ix = 1.0f / d.x;
+    R.iy = 1.0f / d.y;
+    R.iz = 1.0f / d.z;
+    R.fast = slab_fast_ray(slabFast, R.o, R.ix, R.iy, R.iz);
+    R.ix2 = f2(R.ix, R.ix);
+    R.iy2 = f2(R.iy, R.iy);
+    R.iz2 = f2(R.iz, R.iz);
+}
+
 // Both children of interior record `cur`, in the reference's visit order (trace.cu:66-77: near =
 // second child when the ray direction is negative along the split axis).  Only the choice of
 // the next node and of the pushed (far) child depends on the order: "both hit" and "any hit" are
@@ -84,8 +111,8 @@ PT_DEV ChildPair cb_pair(const float4& Q0, const float4& Q1, const float4& Q2, c
     const float loR = slab_lo_x<ALLFAST>(R, f2(Q2.x, Q2.y), f2(Q2.z, Q2.w), f2(Q1.z, Q1.w), tMin, XR);
     const bool isNeg = (negMask & __float_as_uint(Q3.z)) != 0u;
     const uint32_t wL = __float_as_uint(Q3.x), wR = __float_as_uint(Q3.y);
-    const bool hL = XL > loL && tMax > loL;
-    const bool hR = XR > loR && tMax > loR;
+    const bool hL = XL > loL && !(tMax <= loL);   // (a NaN t_max passes: slab_pass_all)
+    const bool hR = XR > loR && !(tMax <= loR);
     const bool takeL = hL && (!hR || !isNeg);
     ChildPair c;
     c.push = hL && hR;
@@ -144,7 +171,7 @@ PT_DEV uint32_t traverse_cb(const float4* __restrict__ cnodes, const float4* __r
     R.ix = rcp_rn(d.x);
     R.iy = rcp_rn(d.y);
     R.iz = rcp_rn(d.z);
-    R.fast = P.slabFast && __builtin_isfinite(R.ix) && __builtin_isfinite(R.iy) && __builtin_isfinite(R.iz);
+    R.fast = slab_fast_ray(P.slabFast != 0, R.o, R.ix, R.iy, R.iz);
     R.ox2 = f2(o.x, o.x);
     R.oy2 = f2(o.y, o.y);
     R.oz2 = f2(o.z, o.z);
@@ -157,7 +184,7 @@ PT_DEV uint32_t traverse_cb(const float4* __restrict__ cnodes, const float4* __r
     auto pop = [&]() -> bool {
         while (sp > 0) {
             const uint2 e = stack[64u * (--sp)];
-            if (tMax > __uint_as_float(e.y)) { cur = e.x; return true; }
+            if (!(tMax <= __uint_as_float(e.y))) { cur = e.x; return true; }
         }
         return false;
     };
@@ -200,9 +227,12 @@ PT_DEV uint32_t traverse_cb(const float4* __restrict__ cnodes, const float4* __r
         }
         // t_max ended the leaf above where it started (the sphere's far-root quirk, ChildPair): boxes
         // dropped for failing an earlier, smaller t_max may pass now.  (A rise undone within the leaf
-        // needs nothing: every dropped box failed a t_max at least as large as the one left.)
-        const bool rose = tMax > tLeaf;
+        // needs nothing: every dropped box failed a t_max at least as large as the one left.)  A NaN
+        // t_max counts as risen above everything (slab_pass_all).
+        const bool rose = !(tMax <= tLeaf);
         if (__ballot(rose) != 0ull && rose) {                  // rare: a uniform test first
+            if (tMax != tMax) slab_pass_all(R);
+            else if (tLeaf != tLeaf) slab_restore(R, d, P.slabFast != 0);
             repair_pending(cnodes, stack, R, negMask, tMin, P.rootWord, leaf0, sp);
             if (STATS) cnt.repairs++;
         }
@@ -259,7 +289,7 @@ PT_DEV void walk_interior(const float4* __restrict__ cnodes, uint2* stack, const
             bool more = sp > 0;
             while (more) {
                 const uint2 e = stack[64u * (--sp)];
-                const bool pass = tMax > __uint_as_float(e.y);
+                const bool pass = !(tMax <= __uint_as_float(e.y));
                 cur = pass ? e.x : cur;
                 more = !pass && sp > 0;
             }
@@ -286,17 +316,25 @@ PT_DEV bool traverse_cb_phase(const float4* __restrict__ cnodes, const float4* _
     R.iy = rcp_fast(d.y);
     R.iz = rcp_fast(d.z);
     {
+        // A traversal resumed with a NaN t_max takes NaN reciprocals (slab_pass_all) through the same
+        // guard: for the rays that reach here with one (NaN origin or direction, see the leaf branch
+        // below) the products are NaN already and this changes nothing.  The fast slab form's per-ray condition (slab_fast_ray) comes out of it too: inside
+        // the guard's range the reciprocals are finite, so only the origin is left to test.
         const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
+        const bool nanT = !fresh && ts.tMax != ts.tMax;
         const bool ok = ax >= 0x1p-125f && ax <= 0x1p125f && ay >= 0x1p-125f && ay <= 0x1p125f &&
-                        az >= 0x1p-125f && az <= 0x1p125f;
+                        az >= 0x1p-125f && az <= 0x1p125f && !nanT;
+        const bool originOk = __builtin_isfinite((o.x + o.y) + o.z);
+        R.fast = P.slabFast != 0 && ok && originOk;
         if (__ballot(!ok) != 0ull) {
-            const float gx = 1.0f / d.x, gy = 1.0f / d.y, gz = 1.0f / d.z;
+            const float qnan = __uint_as_float(0x7fc00000u);
+            const float gx = nanT ? qnan : 1.0f / d.x, gy = nanT ? qnan : 1.0f / d.y, gz = nanT ? qnan : 1.0f / d.z;
             R.ix = ok ? R.ix : gx;
             R.iy = ok ? R.iy : gy;
             R.iz = ok ? R.iz : gz;
+            R.fast = ok ? R.fast : slab_fast_ray(P.slabFast != 0, o, gx, gy, gz);
         }
     }
-    R.fast = P.slabFast && __builtin_isfinite(R.ix) && __builtin_isfinite(R.iy) && __builtin_isfinite(R.iz);
     R.ox2 = f2(o.x, o.x);
     R.oy2 = f2(o.y, o.y);
     R.oz2 = f2(o.z, o.z);
@@ -342,7 +380,14 @@ PT_DEV bool traverse_cb_phase(const float4* __restrict__ cnodes, const float4* _
             // t_max ended the leaf above where it started (the sphere's far-root quirk, ChildPair):
             // boxes dropped for failing an earlier, smaller t_max may pass now.  (A rise undone within
             // the leaf needs nothing: every dropped box failed a t_max at least as large as the one left.)
-            const bool rose = tMax > tLeaf;
+            // A NaN t_max counts as risen, and the reference then visits every node.  This walk does so
+            // only for a ray whose origin or direction holds a NaN -- its slab products are NaN, so every
+            // box passed and was kept all along, and this rebuild keeps every far child too.  For a ray of
+            // numbers it would visit only the boxes the ray's line meets, so the cause of a NaN distance
+            // on such a ray is refused up front: a primitive whose inverse transform is not finite
+            // (pt_set_scene and the scene loader).  What is left -- a quadric's
+            // discriminant overflowing to inf - inf at local coordinates above 1e19 -- is recorded there.
+            const bool rose = !(tMax <= tLeaf);
             if (!NOREPAIR && __ballot(rose) != 0ull && rose) {     // rare: a uniform test first
                 repair_pending(cnodes, stack, R, negMask, tMin, P.rootWord, leaf0, sp);
                 if (STATS) cnt.repairs++;
@@ -352,7 +397,7 @@ PT_DEV bool traverse_cb_phase(const float4* __restrict__ cnodes, const float4* _
             bool more = sp > 0;
             while (more) {
                 const uint2 e = stack[64u * (--sp)];
-                const bool pass = tMax > __uint_as_float(e.y);
+                const bool pass = !(tMax <= __uint_as_float(e.y));
                 cur = pass ? e.x : cur;
                 more = !pass && sp > 0;
             }

@@ -1065,6 +1065,16 @@ PT_API int pt_set_scene(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node
     std::vector<uint8_t> reach(node_count, 0);
     int rc = validate_scene(ctx, nodes, node_count, prims, prim_count, maxDepth, reach);
     if (rc != PT_OK) return rc;
+    // Refused (include/pt_hip.h): a primitive whose inverse transform holds inf or NaN (a zero scale)
+    for (uint32_t i = 0; i < prim_count; ++i)
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c)
+                if (!std::isfinite(prims[i].inv_transform_rows[r][c])) {
+                    char buf[160];
+                    snprintf(buf, sizeof(buf), "pt_set_scene: primitive %u: inv_transform_rows[%d][%d] is not finite "
+                             "(every value must be a finite float)", i, r, c);
+                    return fail(ctx, PT_ERR_ARG, buf);
+                }
     std::vector<float4> hn(2 * (size_t)node_count), hp(4 * (size_t)prim_count), hm(3 * (size_t)prim_count);
     bool slabFast = true;
     for (uint32_t i = 0; i < node_count; ++i) {

@@ -86,6 +86,17 @@ PT_DEV float sqrt_dom(float x)
     const float s = __builtin_fmaf(__builtin_fmaf(-s0, s0, x), h, s0);
     return x > 0.0f ? s : x;
 }
+// sqrt_dom for operands that may also be negative: sqrtf of a negative number (-inf included) is NaN,
+// where sqrt_dom would hand the operand back; -0 gives -0 as sqrtf does.  Domain: +-0, NaN, every
+// negative, and [2^-96, FLT_MAX]; checked for all of it by tools/fp_exhaustive.hip.  One compare and
+// one select more than sqrt_dom.
+PT_DEV float sqrt_dom_neg(float x)
+{
+    const float y = __builtin_amdgcn_rsqf(x);
+    const float s0 = x * y, h = 0.5f * y;
+    const float s = __builtin_fmaf(__builtin_fmaf(-s0, s0, x), h, s0);
+    return x > 0.0f ? s : (x < 0.0f ? __uint_as_float(0x7fc00000u) : x);
+}
 
 // 1 / sqrt_rn(x): a root in sqrt's fast range lies in [2^-48, 2^64], inside rcp's fast range
 PT_DEV float rcp_sqrt_rn(float x)

@@ -10,7 +10,7 @@
 
 #include "../pathtracercuda_amd/csrc/pt_math.h"
 
-#define NSEQ 16
+#define NSEQ 17
 __device__ unsigned long long g_bad[NSEQ];
 __device__ uint32_t g_first[NSEQ][8];
 
@@ -68,6 +68,12 @@ __global__ void check(uint32_t base)
     check_one(14, !dom || __float_as_uint(pt::sqrt_dom(x)) == __float_as_uint(ref_sqrt), xb);
     // normalize_dom's NaN rule: 1 / sqrtf(NaN) through the general path is that same (quiet) NaN
     check_one(15, !qnan || __float_as_uint(pt::rcp_rn(sqrtf(x))) == xb, xb);
+    // sqrt_dom_neg: sqrt_dom's domain and every negative operand, -0 and -inf included: -0 for -0 and a
+    // NaN for the others, as sqrtf gives (which NaN is not compared: an x86 sqrtss returns the default
+    // NaN with its sign bit set, the GPU's sqrtf a positive one)
+    const bool neg = (xb >> 31) != 0u && x == x;
+    const float sn = pt::sqrt_dom_neg(x);
+    check_one(16, !(dom || neg) || (ref_sqrt != ref_sqrt ? sn != sn : __float_as_uint(sn) == __float_as_uint(ref_sqrt)), xb);
 }
 
 int main()
@@ -85,7 +91,7 @@ int main()
     const char* names[NSEQ] = {"rcp_rn", "sqrt_rn", "diag_rcp_raw_all_inputs", "diag_rcp_newton_unguarded",
                                "diag_sqrt_raw_all_inputs", "diag_sqrt_rsq_newton_unguarded", "div_pi", "div_two_pi",
                                "rcp_rn_u", "sqrt_rn_u", "acos_sel", "atan_pos_sel", "atan2_sel_y", "atan2_sel_x",
-                               "sqrt_dom", "nan_through_rcp_sqrt"};
+                               "sqrt_dom", "nan_through_rcp_sqrt", "sqrt_dom_neg"};
     printf("{\n  \"inputs\": 4294967296,\n");
     for (int k = 0; k < NSEQ; ++k) {
         printf("  \"%s\": {\"mismatches\": %llu, \"first\": [", names[k], bad[k]);
