@@ -4,6 +4,7 @@
 #   pathtracercuda_amd/lib/pathtracer     CLI (reference main.cpp headless path)
 #   pathtracercuda_amd/lib/fp_exhaustive  all-inputs check of the kernel's fast 1/x and sqrt (GPU)
 #   pathtracercuda_amd/lib/host_sanitize_check  ASan/UBSan mutation check of the host parsers (CPU)
+#   pathtracercuda_amd/lib/leaf_forms_check  exact vs fast form of the cube leaf test (CPU; `make leafcheck` runs it)
 #   oracle/liboracle.so                   CPU restatement (test infrastructure only)
 #   oracle/_ref/libptref.so               the reference's own source built for the host, when a checkout
 #                                         of it is at $(REF) (test infrastructure only; oracle/Makefile)
@@ -29,7 +30,7 @@ HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fno-slp-vec
 CXXFLAGS ?= -O2 -std=c++17 -ffp-contract=off -fno-fast-math -fPIC -Iinclude -I$(SRC)/host -Wall -Wextra \
             -Wno-unused-parameter -Wno-missing-field-initializers
 
-all: $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer $(LIB)/fp_exhaustive $(LIB)/host_sanitize_check oracle
+all: $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer $(LIB)/fp_exhaustive $(LIB)/host_sanitize_check $(LIB)/leaf_forms_check oracle
 
 $(LIB):
 	mkdir -p $(LIB)
@@ -58,13 +59,21 @@ $(LIB)/host_sanitize_check: tools/host_sanitize_check.cpp $(SAN_SRCS) $(HOST_HDR
 	  -L$(LIB) -lpt_hip -lz -lpthread -Wl,-rpath,'$$ORIGIN'
 sanitize: $(LIB)/host_sanitize_check
 
+# Host check of the cube leaf test's two forms (csrc/pt_leaf_forms.h): a directed grid of special values
+# and 10^8 random rays, under ASan/UBSan; about a minute on one core.
+$(LIB)/leaf_forms_check: tools/leaf_forms_check.cpp $(SRC)/pt_leaf_forms.h | $(LIB)
+	$(CXX) -O2 -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	  -o $@ tools/leaf_forms_check.cpp
+leafcheck: $(LIB)/leaf_forms_check
+	$(LIB)/leaf_forms_check
+
 clean:
 	rm -f $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer
 	$(MAKE) -C oracle clean
 clean-ref:
 	$(MAKE) -C oracle clean-ref
 
-.PHONY: all oracle clean clean-ref sanitize
+.PHONY: all oracle clean clean-ref sanitize leafcheck
 
 # `make -s print-HIPFLAGS`: the flags snapshot builds (tools/snap_rev.sh) reuse
 print-%:

@@ -328,6 +328,12 @@ PT_API int pt_set_strip_units(pt_context *ctx, int mode);
  * walks drop boxes the reference would test (trace.cu:48-98) and results are NOT the reference's on
  * rays that meet the quirk.  Default 1.  Exists so a test can show that a scene exercises the rebuild. */
 PT_API int pt_set_rise_repair(pt_context *ctx, int enabled);
+/* Test knob (negative control): the next pt_set_scene uploads other values than the quadric constants
+ * B, H, J (kept in the device record of every primitive) for every primitive of shape `type` (0..6;
+ * -1 = none, the default): zeros for a quadric shape, so its tests read a wrong quadric and results are
+ * NOT the reference's; NaN for a disk, quad or cube, whose tests must never read the words, so results
+ * stay the reference's.  Exists so a test can show which paths read the constants from the record. */
+PT_API int pt_set_zero_quadric_consts(pt_context *ctx, int type);
 /* Run-ahead across render() calls: a launch of 3..64 samples per pixel (the reference's
  * render(camera, 8, ...) calls, main.cpp:272-279) lets the lanes whose pixels are done go on with the
  * pixel's next call (same XORWOW stream) until their tile ends, and keeps per pixel the colour sum,

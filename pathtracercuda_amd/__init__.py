@@ -388,6 +388,13 @@ class Pathtracer:
         for c in self._contexts():
             N.check_ctx(N.hip().pt_set_rise_repair(c, int(bool(enabled))), c)
 
+    def set_zero_quadric_consts(self, shape_type: int) -> None:
+        """Test knob (pt_set_zero_quadric_consts): the next scene upload replaces the quadric constants of
+        every primitive of this shape type (-1 = none): zeros for a quadric (results are NOT the reference's),
+        NaN for a disk, quad or cube (never read: results unchanged)."""
+        for c in self._contexts():
+            N.check_ctx(N.hip().pt_set_zero_quadric_consts(c, int(shape_type)), c)
+
     def set_sample_groups(self, mode: int) -> None:
         """Speculative sample groups (pt_set_sample_groups): 0 = automatic, 1 = off, G >= 2 = always G."""
         for c in self._contexts():

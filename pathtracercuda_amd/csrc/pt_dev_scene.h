@@ -21,7 +21,7 @@ struct TraceParams {
     float4* accum;              // rows x width, local
     uint32_t* rng;              // 6 planes of rows x width (d, v0..v4)
     const float4* nodes;        // 2 per node: (min.xyz, max.x), (max.yz, offset bits, pca bits)
-    const float4* prims;        // 4 per prim: row0, row1, row2, (type bits, 0, 0, 0)
+    const float4* prims;        // 4 per prim: row0, row1, row2, (type bits, quadric B, H, J)
     const float4* mats;         // 3 per prim: (base.xyz, roughness), (emissive.xyz, metal), (tex, type)
     const DevTex* textures;     // 64 entries
     unsigned long long* stats;  // 6 counters (instrumented variant only)
@@ -188,11 +188,11 @@ PT_DEV LocalRay to_local(const float4& P0, const float4& P1, const float4& r2, f
 // A = C = 1 and D = E = F = G = I = 0; B, H, J vary.  Evaluated with the nonzero terms in the
 // template's order; dropping the exact +-0 terms of D..G and I cannot change a, b or c except for
 // the sign of a zero, which no later operation observes (DESIGN.md "Quadric terms").
-PT_DEV bool quadric_roots(uint32_t type, const LocalRay& r, float& t0, float& t1)
+// B, H and J are per-primitive constants read from the record (quadric_consts, written by
+// pt_set_scene) instead of being rebuilt from the type by compares and selects in every test;
+// 2 B stays a multiply (exact, one VALU instruction, as before; the record has no fourth free word).
+PT_DEV bool quadric_roots(float B, float Hc, float J, const LocalRay& r, float& t0, float& t1)
 {
-    const float B = (type == SPHERE) ? 1.0f : (type == CONE ? -1.0f : 0.0f);
-    const float Hc = (type == PARABOLOID) ? -1.0f : 0.0f;
-    const float J = (type == SPHERE || type == CYLINDER) ? -1.0f : 0.0f;
     const f3 o = r.o, d = r.d;
     const float a = (d.x * d.x + (B * d.y) * d.y) + d.z * d.z;
     const float b = (((2.0f * o.x) * d.x + ((2.0f * B) * o.y) * d.y) + (2.0f * o.z) * d.z) + Hc * d.y;
@@ -213,6 +213,7 @@ PT_DEV bool quadric_roots(uint32_t type, const LocalRay& r, float& t0, float& t1
 struct PrimRec {
     float4 r0, r1, r2;
     uint32_t type;
+    float B, Hc, J;             // quadric constants (quadric_consts), zero for planes and cubes
 };
 
 PT_DEV PrimRec load_prim(const float4* __restrict__ prims, uint32_t p)
@@ -221,7 +222,11 @@ PT_DEV PrimRec load_prim(const float4* __restrict__ prims, uint32_t p)
     q.r0 = prims[4 * p + 0];
     q.r1 = prims[4 * p + 1];
     q.r2 = prims[4 * p + 2];
-    q.type = __float_as_uint(prims[4 * p + 3].x);
+    const float4 q3 = prims[4 * p + 3];
+    q.type = __float_as_uint(q3.x);
+    q.B = q3.y;
+    q.Hc = q3.z;
+    q.J = q3.w;
     return q;
 }
 
@@ -230,6 +235,11 @@ PT_DEV bool prim_hit_rec(const PrimRec& q, f3 o, f3 d, float tMin, float tMax, f
 {
     const uint32_t type = q.type;
     const LocalRay r = to_local(q.r0, q.r1, q.r2, o, d);
+    // The constants stay part of the record's one fetch: without this the compiler loads the fourth
+    // quad's type word alone and sinks a second load of y, z, w into the quadric path, where its
+    // whole latency is exposed in front of the first multiply.
+    float qB = q.B, qH = q.Hc, qJ = q.J;
+    asm volatile("" : "+v"(qB), "+v"(qH), "+v"(qJ));
     if (type == DISK || type == QUAD) {                    // Hittable.inl:205-235, 299-329
         if (r.d.y == 0.0f) return false;
         const float t = -r.o.y / r.d.y;
@@ -245,24 +255,13 @@ PT_DEV bool prim_hit_rec(const PrimRec& q, f3 o, f3 d, float tMin, float tMax, f
         return true;
     }
     if (type == CUBE) {                                     // Hittable.inl:331-358, AABB.inl:46-69
-        float lo = tMin, hi = tMax;
-        const float ox[3] = {r.o.x, r.o.y, r.o.z};
-        const float dx[3] = {r.d.x, r.d.y, r.d.z};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float invD = rcp_rn(dx[a]);
-            float t0 = (-1.0f - ox[a]) * invD;
-            float t1 = (1.0f - ox[a]) * invD;
-            if (invD < 0.0f) { const float tmp = t0; t0 = t1; t1 = tmp; }
-            lo = t0 > lo ? t0 : lo;
-            hi = t1 < hi ? t1 : hi;
-        }
-        if (hi <= lo) return false;
-        tOut = lo;
-        return true;
+        // The reference's loop (pt_leaf_forms.h, which also holds a min/max form behind one wave-uniform
+        // guard: exact -- tools/leaf_forms_check.cpp -- but its gain on top of the record's constants did
+        // not clear the same-box protocol on the headline, DESIGN.md Appendix A, so it is not used).
+        return cube_hit_exact(r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, tMin, tMax, tOut);
     }
     float t0 = 0.0f, t1 = 0.0f;                             // quadrics
-    if (!quadric_roots(type, r, t0, t1) || t0 > tMax || t1 <= tMin) return false;
+    if (!quadric_roots(qB, qH, qJ, r, t0, t1) || t0 > tMax || t1 <= tMin) return false;
     if (type == SPHERE) {                                   // Hittable.inl:158 (far-root quirk kept)
         tOut = t0 > tMin ? t0 : t1;
         return true;

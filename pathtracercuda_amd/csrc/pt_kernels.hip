@@ -36,6 +36,7 @@
 #include <chrono>
 
 #include "pt_math.h"
+#include "pt_leaf_forms.h"
 #include "../../include/pt_hip.h"
 
 using namespace pt;
@@ -487,6 +488,7 @@ struct pt_context {
     uint32_t cnodeCount = 0, rootWord = 0;
     bool dfsOrder = true;             // leaves hold their primitives in DFS order (repair_pending)
     bool riseRepair = true;           // pt_set_rise_repair (tests' negative control only)
+    int zeroConstsType = -1;          // pt_set_zero_quadric_consts (tests' negative control only)
     // run-ahead across render() calls (MODE 4): the stash and the key it was made under
     uint32_t* ahead = nullptr;        // [kAheadWords][pixels]
     bool aheadValid = false;          // the last launch made a stash
@@ -1135,7 +1137,12 @@ PT_API int pt_set_scene(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node
         hp[4 * i + 0] = make_float4(R[0][0], R[1][0], R[0][1], R[1][1]);
         hp[4 * i + 1] = make_float4(R[0][2], R[1][2], R[0][3], R[1][3]);
         hp[4 * i + 2] = make_float4(R[2][0], R[2][1], R[2][2], R[2][3]);
-        hp[4 * i + 3] = make_float4(u2f(h.type), 0.0f, 0.0f, 0.0f);
+        // fourth quad: the type and the shape's quadric constants (quadric_roots reads them here)
+        float qB, qH, qJ;
+        quadric_consts(h.type, qB, qH, qJ);
+        if ((int)h.type == ctx->zeroConstsType)                      // test knob, see pt_hip.h: zeros for a
+            qB = qH = qJ = (h.type == 2u || h.type >= 5u) ? std::nanf("") : 0.0f;   // quadric, NaN for a plane or cube
+        hp[4 * i + 3] = make_float4(u2f(h.type), qB, qH, qJ);
         hm[3 * i] = make_float4(h.base_color[0], h.base_color[1], h.base_color[2], h.roughness);
         hm[3 * i + 1] = make_float4(h.emissive[0], h.emissive[1], h.emissive[2], h.metalness);
         hm[3 * i + 2] = make_float4(u2f(h.texture_index), u2f(h.material_type), 0.0f, 0.0f);
@@ -1847,6 +1854,13 @@ PT_API int pt_set_rise_repair(pt_context* ctx, int enabled)
 {
     if (!ctx || enabled < 0 || enabled > 1) return PT_ERR_ARG;
     ctx->riseRepair = enabled != 0;
+    return PT_OK;
+}
+
+PT_API int pt_set_zero_quadric_consts(pt_context* ctx, int type)
+{
+    if (!ctx || type < -1 || type > 6) return PT_ERR_ARG;
+    ctx->zeroConstsType = type;
     return PT_OK;
 }
 

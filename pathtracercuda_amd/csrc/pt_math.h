@@ -60,7 +60,10 @@ PT_DEV float sqrt_rn(float x)
 // sequences apply, otherwise both general paths run -- the same values either way.  (Round 5 also
 // merged pairs of roots in shading this way, +0.62 %; round 6 replaced them by sqrt_dom where the
 // operand's range is known, and the merge of the three ray reciprocals and of the cube test's three
-// measured -1.1 % and is not used.)
+// behind one DIVERGENT guard measured -1.1 % and is not used.  The ray reciprocals now share one
+// WAVE-UNIFORM guard instead (traverse_cb_phase); the same for the cube test, with a min/max form on
+// that guard, measured -0.5 % in time on top of its parent, inside the run-to-run range on the
+// headline, and is not used either: pt_leaf_forms.h, DESIGN.md Appendix A.)
 PT_DEV bool sqrt_fast_ok(float x) { return __float_as_uint(x) - 0x0f800000u <= 0x7f7fffffu - 0x0f800000u; }
 PT_DEV float rcp_fast(float x)
 {
