@@ -358,6 +358,11 @@ PT_API int pt_set_group_lookback(pt_context *ctx, uint32_t far, uint32_t near);
 PT_API int pt_last_sample_groups(const pt_context *ctx);
 /* The trace-kernel variant the last launch ran (its main pass; diagnostics and tests). */
 PT_API int pt_last_variant(const pt_context *ctx);
+/* The last trace launch of the context (the main pass of pt_render, the last round of
+ * pt_render_adaptive; diagnostics and tests), 4 words: dynamic LDS bytes of a workgroup; what it staged
+ * in LDS (0 nothing -- the scene is read through the caches --, 1 the child-box records or the nodes,
+ * 2 the primitives too); waves per workgroup; workgroups launched. */
+PT_API int pt_last_launch(const pt_context *ctx, uint32_t *dst);
 PT_API int pt_read_group_stats(const pt_context *ctx, uint32_t *dst);
 PT_API int pt_read_group_log_counts(pt_context *ctx, uint32_t *dst, size_t count);
 /* Diagnostics: one word plane of the per-pixel fold state (rows x width; word 16 = dead-end flag,

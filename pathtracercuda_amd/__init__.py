@@ -410,6 +410,15 @@ class Pathtracer:
         """Trace-kernel variant of the last launch's main pass (a device group: device 0's)."""
         return int(N.hip().pt_last_variant(self._contexts()[0]))
 
+    @property
+    def last_launch(self) -> Dict[str, int]:
+        """The last trace launch (pt_last_launch): dynamic LDS bytes of a workgroup, what it staged
+        in LDS (0 nothing, 1 records or nodes, 2 primitives too), waves per workgroup, workgroups."""
+        self._single("last_launch")
+        out = (C.c_uint32 * 4)()
+        N.check_ctx(N.hip().pt_last_launch(self._ctx, out), self._ctx)
+        return {"lds_bytes": int(out[0]), "staged": int(out[1]), "waves_per_group": int(out[2]), "groups": int(out[3])}
+
     def set_patch_rounds(self, rounds: int) -> None:
         for c in self._contexts():
             N.check_ctx(N.hip().pt_set_patch_rounds(c, int(rounds)), c)

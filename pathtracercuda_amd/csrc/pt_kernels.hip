@@ -506,6 +506,7 @@ struct pt_context {
     uint32_t nodeCount = 0, primCount = 0, stackDepth = 1;
     bool slabFast = true;
     int variant = 0;
+    uint32_t lastLaunch[4] = {};      // pt_last_launch: LDS bytes, staging level, waves per workgroup, workgroups
     DevTex* texTable = nullptr;
     DevTex hostTex[PT_MAX_TEXTURES] = {};
     uint32_t skybox = 0;
@@ -602,6 +603,19 @@ static int fail(pt_context* ctx, int code, const char* msg)
     return code;
 }
 
+// What launch_one launched last on this host thread (a device group renders one context per thread):
+// dynamic LDS bytes of a workgroup, staging level, waves per workgroup, workgroups.  launch_one has
+// no context; render_impl copies it after its main pass (pt_last_launch; diagnostics and tests).
+static thread_local uint32_t g_lastLaunch[4] = {};
+
+static inline void note_launch(size_t lds, int sl, int wpb, unsigned groups)
+{
+    g_lastLaunch[0] = (uint32_t)lds;
+    g_lastLaunch[1] = (uint32_t)sl;
+    g_lastLaunch[2] = (uint32_t)wpb;
+    g_lastLaunch[3] = groups;
+}
+
 // Kernel variants (workgroup size, scene staged in LDS or read through the caches).
 template <bool STATS, int SL, int WPB, int WW, int MINW, bool PERSIST = false, int MODE = 0>
 static hipError_t launch_one(const TraceParams& P, hipStream_t stream)
@@ -659,6 +673,7 @@ static hipError_t launch_one(const TraceParams& P, hipStream_t stream)
             // kernel on a grid of its own size, every wave taking its slot from the cursor (one build
             // per variant instead of two)
             if (!P.occCap && blocks <= (unsigned)cap) {
+                note_launch(lds, SL, WPB, blocks);
                 trace_kernel<STATS, SL, WPB, WW, MINW, PERSIST, MODE><<<blocks, WPB * 64, lds, stream>>>(P);
                 return hipGetLastError();
             }
@@ -680,9 +695,11 @@ static hipError_t launch_one(const TraceParams& P, hipStream_t stream)
             Q.prio[1] = std::max(Q.prio[1], Q.prio[0]);
             Q.prio[2] = std::max(Q.prio[2], Q.prio[1]);
         }
+        note_launch(lds, SL, WPB, (unsigned)cap);
         trace_kernel<STATS, SL, WPB, WW, MINW, PERSIST, MODE><<<(unsigned)cap, WPB * 64, lds, stream>>>(Q);
         return hipGetLastError();
     }
+    note_launch(lds, SL, WPB, blocks);
     trace_kernel<STATS, SL, WPB, WW, MINW, PERSIST, MODE><<<blocks, WPB * 64, lds, stream>>>(P);
     return hipGetLastError();
 }
@@ -1785,6 +1802,7 @@ static int render_impl(pt_context* ctx, const pt_camera* cam, uint32_t spp, uint
                                 : ahead ? launch_ahead(variant, P, ctx->stream)
                                 : (K > 1 ? launch_strip(variant, P, ctx->stream) : launch_variant<false>(variant, P, ctx->stream)));
     }
+    memcpy(ctx->lastLaunch, g_lastLaunch, sizeof(ctx->lastLaunch));
     if (aheadMake) {
         ctx->aheadValid = true;
         ctx->aheadCam = *cam;
@@ -1899,6 +1917,13 @@ PT_API int pt_last_sample_groups(const pt_context* ctx)
 }
 
 PT_API int pt_last_variant(const pt_context* ctx) { return ctx ? ctx->lastVariant : 0; }
+
+PT_API int pt_last_launch(const pt_context* ctx, uint32_t* dst)
+{
+    if (!ctx || !dst) return PT_ERR_ARG;
+    memcpy(dst, ctx->lastLaunch, sizeof(ctx->lastLaunch));
+    return PT_OK;
+}
 
 
 PT_API int pt_read_group_log_counts(pt_context* ctx, uint32_t* dst, size_t count)
@@ -2087,6 +2112,7 @@ PT_API int pt_render_adaptive(pt_context* ctx, const pt_camera* camera, const pt
         ++ctx->adSteps;
         samples += (uint64_t)count * ap.spp;
     }
+    memcpy(ctx->lastLaunch, g_lastLaunch, sizeof(ctx->lastLaunch));
     PT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     PT_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
     float ms = 0.0f;

@@ -144,3 +144,49 @@ def rise_pair_bvh(aabbs) -> Tuple[List[Node], List[int]]:
     r_lo, r_hi = _union([box[0], box[1], box[2]])
     nodes = [(r_lo, r_hi, 4, 2 << 8), (n_lo, n_hi, 3, 2 << 8), leaf[2], leaf[0], leaf[1]]
     return nodes, order
+
+
+def check_tree(nodes: Sequence[Node], prim_count: int) -> int:
+    """The reference's rules for a BVH (BVH.cpp's build and trace.cu's walk rely on them): every
+    interior node has two children, the first is the next node and the second lies after the whole
+    first subtree, every node is reached exactly once from the root, and the leaves hold non-empty
+    primitive ranges that together cover [0, prim_count) exactly once.  Returns the depth (nodes on
+    the longest root-to-leaf path; the reference's 32-entry stack holds depth <= 33)."""
+    seen = [False] * len(nodes)
+    ranges = []
+    depth = 0
+    st = [(0, 1)]
+    while st:
+        i, d = st.pop()
+        assert 0 <= i < len(nodes) and not seen[i], f"node {i} reached twice or out of range"
+        seen[i] = True
+        depth = max(depth, d)
+        _, _, off, pca = nodes[i]
+        if (pca >> 16) != 0:
+            ranges.append((off, off + (pca >> 16)))
+        else:
+            assert ((pca >> 8) & 0xFF) <= 2, f"node {i}: split axis"
+            assert i + 1 < off < len(nodes), f"node {i}: second child {off} not after the first subtree"
+            st.append((off, d + 1))
+            st.append((i + 1, d + 1))
+    assert all(seen), "unreachable nodes"
+    ranges.sort()
+    assert ranges[0][0] == 0 and ranges[-1][1] == prim_count, "leaf ranges do not cover the primitives"
+    assert all(a[1] == b[0] for a, b in zip(ranges, ranges[1:])), "leaf ranges overlap or leave a gap"
+    return depth
+
+
+def dfs_ordered(nodes: Sequence[Node]) -> bool:
+    """pt_set_scene's dfsOrder: under every interior node the first subtree's primitives lie below the
+    second subtree's (what repair_pending needs to find a leaf's path)."""
+    first, last = [0] * len(nodes), [0] * len(nodes)
+    ok = True
+    for i in range(len(nodes) - 1, -1, -1):
+        _, _, off, pca = nodes[i]
+        if (pca >> 16) != 0:
+            first[i], last[i] = off, off + (pca >> 16) - 1
+        else:
+            a, b = i + 1, off
+            first[i], last[i] = min(first[a], first[b]), max(last[a], last[b])
+            ok = ok and last[a] < first[b]
+    return ok

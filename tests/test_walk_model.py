@@ -126,16 +126,20 @@ def repair(nodes, first, o, d, negmask, leaf_off):
     return stack
 
 
-def cb_walk(nodes, first, o, d, ray_id, rise_all=False, rebuild=True):
+def cb_walk(nodes, first, o, d, ray_id, rise_all=False, rebuild=True, with_peak=False, stop_rows=0):
     """The child-box walk: far child kept when hit now (or, rise_all, whenever the ray meets its
     box), re-tested (t_max > lo) when popped; the pending set rebuilt after a leaf raised t_max
-    (rebuild=False: rounds 1-3, without it)."""
+    (rebuild=False: rounds 1-3, without it).  with_peak: also returns the stack rows the walk used
+    -- the pending entries at an interior visit plus the one the kernel writes above the top there
+    (walk_interior), at its peak; pt_set_scene sizes the LDS rows to this number's bound.  stop_rows:
+    return as soon as that many rows are in use (for scenes where every ray visits every node)."""
     negmask = (d[0] < 0) | ((d[1] < 0) << 1) | ((d[2] < 0) << 2)
     tests, stack, tmax = [], [], F(np.finfo(np.float32).max)
     lo0, x0 = lo_x(*box(nodes[0]), o, d)
     if not (x0 > lo0 and tmax > lo0):
-        return tests
+        return (tests, 0) if with_peak else tests
     cur = 0
+    peak = 0
 
     def pop():
         while stack:
@@ -158,6 +162,9 @@ def cb_walk(nodes, first, o, d, ray_id, rise_all=False, rebuild=True):
                 stack[:] = repair(nodes, first, o, d, negmask, n.offset)
             cur = pop()
             continue
+        peak = max(peak, len(stack) + 1)
+        if stop_rows and peak >= stop_rows:
+            break
         a, b = cur + 1, n.offset
         loa, xa = lo_x(*box(nodes[a]), o, d)
         lob, xb = lo_x(*box(nodes[b]), o, d)
@@ -174,7 +181,7 @@ def cb_walk(nodes, first, o, d, ray_id, rise_all=False, rebuild=True):
             cur = far
         else:
             cur = pop()
-    return tests
+    return (tests, peak) if with_peak else tests
 
 
 def rays(nodes, n, seed):
