@@ -212,6 +212,26 @@ public:
     AdaptiveResult renderAdaptive(const Camera& camera, uint32_t spp, uint32_t minCalls, uint32_t maxCalls, float tolerance,
                                   float floor = 0.01f, bool reset = true);
     bool adaptive() const { return m_adaptive; }     // the buffer holds an adaptive render
+    // First-hit feature buffers and the edge-avoiding a-trous denoiser (pt_render_features, pt_denoise,
+    // pt_hip.h).  renderFeatures traces each pixel's first-sample ray and keeps three float4 planes (albedo +
+    // primitive, normal + distance, position + flags); featurePlane returns one (borrowed, rows x width x 4).
+    // denoise filters the image guided by them: afterwards getHDRImageData / getImageData return the
+    // denoised image until the next render or scene change; the accumulation itself is not touched, so
+    // rendering continues as if the pass had not run.  sigmaColor <= 0: automatic (the factor of
+    // PT_DENOISE_DEFAULT_SIGMA_FACTOR times the median luminance of the kept pixels).  Single device only.
+    struct DenoiseOptions {
+        uint32_t iterations = PT_DENOISE_DEFAULT_ITERATIONS;
+        float sigmaColor = 0.0f;
+        float sigmaPlane = PT_DENOISE_DEFAULT_SIGMA_PLANE;
+        uint32_t normalPowerLog2 = PT_DENOISE_DEFAULT_NORMAL_POWER_LOG2;
+        uint32_t flags = PT_DENOISE_DEFAULT_FLAGS;
+        uint32_t staging = 0;
+    };
+    void renderFeatures(const Camera& camera);
+    const float* featurePlane(uint32_t plane);
+    float denoise(const DenoiseOptions& options);    // returns the sigma_color used
+    float denoise() { return denoise(DenoiseOptions()); }
+    bool denoised() const { return m_denoised; }     // the image calls return the denoised image
     float getTiming() const;
     uint32_t loadTexture(const char* path);
     void setSkyboxTextureHandle(uint32_t handle);
@@ -244,6 +264,8 @@ private:
     pt_group* m_group = nullptr;
     float m_gatherMs = 0.0f;
     bool m_adaptive = false;
+    bool m_denoised = false;
+    std::vector<float> m_featureBuffer;
     BVH m_bvh;
     void allocHostBuffers();
     void check(int rc, const char* what) const;
@@ -266,6 +288,7 @@ struct Params {
     bool m_singleLaunch = true;      // run all chunks in one launch (bit-identical; CLI -call_loop: false)
     float m_adaptive = -1.0f;        // CLI -adaptive <tolerance>: >= 0 renders adaptively, m_spp is the budget
     unsigned int m_minSpp = 0;       // CLI -minspp: samples every pixel gets (0 = two calls)
+    unsigned int m_denoise = 0;      // CLI -denoise [N]: a-trous iterations applied before the image is written (0 = off)
 };
 
 Camera loadScene(Pathtracer& pathtracer, const Params& params);

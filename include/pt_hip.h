@@ -369,7 +369,107 @@ PT_API int pt_read_group_log_counts(pt_context *ctx, uint32_t *dst, size_t count
  * 7 = samples done, 8 = draw-pair offset), or with words 19 / 20 / 21 the statistics the next
  * launch's guesses use (float): draw pairs per sample, odd-length fraction, variance. */
 PT_API int pt_read_group_fold(pt_context *ctx, uint32_t word, uint32_t *dst);
+/* The message of the context's last failed call.  With ctx = NULL: the message of the calling thread's
+ * last failed context-free call (pt_denoise_image). */
 PT_API const char *pt_last_error(const pt_context *ctx);
+
+/* ---- First-hit feature buffers ------------------------------------------------------------------
+ * pt_render_features traces one ray per pixel -- the pixel's FIRST sample of a reset render: the XORWOW
+ * state is curand_init(1984 + x + y * width, 0, 0) of the global pixel, computed in the kernel (the
+ * context's RNG buffer is not read), and two uniforms are drawn, x then y, as for every camera ray --
+ * with the reference's loop over the BVH (valid for every scene pt_set_scene accepts), and stores the
+ * closest hit in three planes of rows x width float4 (local row order), allocated on first use:
+ *   plane 0: x, y, z = the material's base colour as shading forms it (after the texture lookup and
+ *            pow 2.2 for a textured material); w = the primitive index as uint32 bits, 0xffffffff on a miss
+ *   plane 1: x, y, z = the world normal, turned against the ray as shading uses it; w = the hit distance t
+ *   plane 2: x, y, z = the world position of the hit; w = flags as uint32 bits: PT_FEATURE_HIT,
+ *            PT_FEATURE_EMISSIVE (any component of the material's emission != 0)
+ * On a miss every float is +0 and the flags word is 0.  The pass reads and writes nothing of the render
+ * state (accumulation, RNG, moments, tile costs and order, run-ahead stash, frame counter), so it
+ * is reproducible, the same for every band partition, and a render continues after it as if it had
+ * not run.  PT_ERR_STATE without a scene.  A scene or texture change voids the planes. */
+#define PT_FEATURE_HIT 1u
+#define PT_FEATURE_EMISSIVE 2u
+PT_API int pt_render_features(pt_context *ctx, const pt_camera *camera);
+/* One plane (0..2) of the last pt_render_features: rows x width float4.  PT_ERR_STATE if there is none. */
+PT_API int pt_read_features(pt_context *ctx, uint32_t plane, float *dst);
+
+/* ---- Edge-avoiding a-trous denoiser -------------------------------------------------------------
+ * Dammertz et al.'s a-trous filter (B3 spline taps, 5 x 5, step doubling and colour sigma halving per
+ * level) guided by the feature planes, with rational edge-stopping weights (+ - x /, compares and selects
+ * only: no exp) and a scale-free plane-distance term, so the result is reproducible word for word.
+ * All float32, no contraction, in exactly these operations (tests/denoise_model.py restates them):
+ *
+ * Per pixel p: colour C (3 floats); A = plane 0 xyz, id = plane 0 w; N = plane 1 xyz, t = plane 1 w;
+ * P = plane 2 xyz, flags = plane 2 w.
+ * Prepare:
+ *     keep_p = HIT && !EMISSIVE && every component x of C, N, P has x - x == 0
+ *     D_p    = DEMODULATE ? (A > 1/64 ? A : 1/64) per channel : 1
+ *     I_p    = C_p / D_p                                       (IEEE division, per channel)
+ * Iteration i = 0 .. iterations - 1, step s = 1 << i, sigma_i = sigma_color * 2^-i (exact):
+ *     for a kept p:  sumW = 0, sumI = (0, 0, 0);  m = sigma_plane * t_p;  mm = m * m;  ss = sigma_i * sigma_i
+ *       for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), q = p + s * (dx, dy);
+ *       q is skipped (by a select, never by a zero weight) when it is outside the image, when !keep_q,
+ *       or when SAME_PRIMITIVE is set and id_q != id_p; otherwise
+ *         h  = k[|dx|] * k[|dy|],  k = {3/8, 1/4, 1/16}
+ *         c  = (N_p.x * N_q.x + N_p.y * N_q.y) + N_p.z * N_q.z;  c = c > 0 ? c : 0;
+ *              normal_power_log2 times: c = c * c;               w_n = c
+ *         e  = P_q - P_p;  g = (N_p.x * e.x + N_p.y * e.y) + N_p.z * e.z;  w_p = 1 / (1 + (g * g) / mm)
+ *         d  = I_q - I_p;  d2 = (d.r * d.r + d.g * d.g) + d.b * d.b;       w_c = 1 / (1 + d2 / ss)
+ *         w  = ((h * w_n) * w_p) * w_c;   sumW = sumW + w;   sumI = sumI + w * I_q  (per channel)
+ *       I'_p = sumI / sumW
+ *     for a p that is not kept: I'_p = I_p
+ * Final:  out_p = keep_p ? I_p * D_p : C_p;  out.w = 1
+ * A NaN or infinite pixel is not kept: it passes through unchanged and never reaches a neighbour.
+ *
+ * Every iteration is one kernel launch between two buffers.  `staging`: 0 = automatic (a workgroup's
+ * tile and its halo of 2 s pixels are staged in LDS for the steps where that wins -- s = 1 and 2, measured --
+ * and the taps are read through the caches otherwise), 1 = staged for every step that fits (s <= 4), 2 = never staged; tests
+ * and A/B only: the words are the same.
+ * Accepted: iterations 1..8, sigma_color > 0, sigma_plane >= 1e-6, normal_power_log2 0..7, flags within
+ * the two bits, staging 0..2; anything else (a NaN included) is PT_ERR_ARG and the message names the field. */
+#define PT_DENOISE_DEMODULATE 1u
+#define PT_DENOISE_SAME_PRIMITIVE 2u
+#define PT_DENOISE_TILE_W 32 /* the filter's workgroup tile (pixels) */
+#define PT_DENOISE_TILE_H 8
+/* Defaults of the layers above (C++ Pathtracer::denoise, Python, the CLI's -denoise), chosen by the sweep of
+ * tools/denoise_probe.py (profiles/denoise_probe.json).  The automatic sigma_color is
+ * SIGMA_FACTOR x the median luminance (0.2126, 0.7152, 0.0722) of the kept pixels' I_p, computed on the
+ * host: the device rule stays free of a reduction whose order would have to be specified. */
+#define PT_DENOISE_DEFAULT_ITERATIONS 5
+#define PT_DENOISE_DEFAULT_SIGMA_FACTOR 4.0f
+#define PT_DENOISE_DEFAULT_SIGMA_PLANE 0.005f
+#define PT_DENOISE_DEFAULT_NORMAL_POWER_LOG2 3
+#define PT_DENOISE_DEFAULT_FLAGS 1u
+typedef struct pt_denoise_params {
+    uint32_t iterations;
+    float sigma_color;       /* in units of the (demodulated) colour */
+    float sigma_plane;       /* relative to the hit distance */
+    uint32_t normal_power_log2;
+    uint32_t flags;
+    uint32_t staging;
+} pt_denoise_params;
+
+/* Filters the context's image: C = accumulation * (1 / max(frames, 1)), the HDR read-out's arithmetic, or,
+ * when the buffer holds an adaptive render, accumulation / n per pixel (pt_read_adaptive_hdr's; `frames`
+ * is not used then); features = the planes of the last pt_render_features.  The accumulation is not
+ * changed.  PT_ERR_STATE, naming the reason, when there are no feature planes or the scene or a texture
+ * changed since; PT_ERR_ARG, naming the reason, on a context that does not hold the whole frame (the
+ * filter needs every pixel's neighbours: gather the frame and use pt_denoise_image). */
+PT_API int pt_denoise(pt_context *ctx, uint32_t frames, const pt_denoise_params *params);
+/* hipEvent times in ms of the last pt_denoise's kernels, 10 floats: prepare, iterations 0..7 (0 for
+ * those not run), finish; and of the last pt_render_features (one float).  Measurements only. */
+PT_API int pt_read_denoise_timing(pt_context *ctx, float *dst);
+PT_API int pt_read_features_timing(pt_context *ctx, float *dst);
+/* The last pt_denoise's result (rows x width float4, w = 1), and its tonemap (pt_tonemap's arithmetic with
+ * divisor 1; RGBA8).  PT_ERR_STATE when there is none. */
+PT_API int pt_read_denoised(pt_context *ctx, float *dst);
+PT_API int pt_tonemap_denoised(pt_context *ctx, uint8_t *dst);
+/* The same filter on host arrays, without a context: color, plane0..2 and out are height x width float4
+ * (color's w is ignored).  For a frame gathered from several devices, and for tests.  Errors:
+ * pt_last_error(NULL). */
+PT_API int pt_denoise_image(int device, uint32_t width, uint32_t height, const float *color, const float *plane0,
+                            const float *plane1, const float *plane2, const pt_denoise_params *params, float *out);
 
 /* ---- Multi-device group (one process, one context per GPU, RCCL over xGMI) -------------------
  * Replaces the reference's hard-coded single device (Pathtracer.cpp:40: cudaSetDevice(0)) behind

@@ -79,6 +79,17 @@ PT_API int pth_renderer_render(pth_renderer *r, const pt_camera *camera, uint32_
 PT_API int pth_renderer_render_adaptive(pth_renderer *r, const pt_camera *camera, const pt_adaptive_params *params,
                                         pt_adaptive_result *result);
 PT_API int pth_renderer_adaptive(const pth_renderer *r);
+/* Pathtracer::renderFeatures / featurePlane / denoise (pt_render_features, pt_denoise, pt_hip.h; single
+ * device).  pth_renderer_feature_plane: plane 0..2, a borrowed pointer (rows x width float4) valid until
+ * the next call, null on error.  pth_renderer_denoise: with auto_sigma != 0 params->sigma_color is not
+ * read: the host computes it (PT_DENOISE_DEFAULT_SIGMA_FACTOR x the median luminance of the kept pixels);
+ * sigma_used (optional) receives the value the filter ran with.  Afterwards pth_renderer_hdr /
+ * pth_renderer_image return the denoised image, and pth_renderer_denoised is 1, until the next render or
+ * scene change; the accumulation is not touched. */
+PT_API int pth_renderer_features(pth_renderer *r, const pt_camera *camera);
+PT_API const float *pth_renderer_feature_plane(pth_renderer *r, uint32_t plane);
+PT_API int pth_renderer_denoise(pth_renderer *r, const pt_denoise_params *params, int auto_sigma, float *sigma_used);
+PT_API int pth_renderer_denoised(const pth_renderer *r);
 PT_API float pth_renderer_timing(const pth_renderer *r);
 PT_API uint32_t pth_renderer_frames(const pth_renderer *r);
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer *r);

@@ -25,7 +25,8 @@ from . import _native as N
 from ._native import PathtracerError, PtBvhNode, PtCamera, PtHittable, PtRenderStats, device_count
 
 __all__ = ["Pathtracer", "Scene", "make_camera", "camera_rotate", "camera_translate", "radians", "device_count", "PathtracerError", "PtCamera",
-           "PtBvhNode", "PtHittable", "write_png", "write_hdr", "HITTABLE_TYPES", "MATERIAL_TYPES"]
+           "PtBvhNode", "PtHittable", "write_png", "write_hdr", "HITTABLE_TYPES", "MATERIAL_TYPES", "denoise_image",
+           "denoise_params", "auto_sigma_color", "denoise_keep_mask", "DENOISE_DEFAULTS", "DENOISE_SIGMA_FACTOR"]
 
 HITTABLE_TYPES = ["SPHERE", "CYLINDER", "DISK", "CONE", "PARABOLOID", "QUAD", "CUBE"]   # Hittable.h:9-12
 MATERIAL_TYPES = ["LAMBERT", "GGX", "LAMBERT_GGX"]                                     # Material.h:9-12
@@ -70,6 +71,98 @@ def write_hdr(path: str, rgba: np.ndarray, flip: bool = True) -> None:
     a = np.ascontiguousarray(rgba, dtype=np.float32)
     h, w = a.shape[:2]
     N.check_host(N.host().pth_write_hdr(os.fsencode(path), w, h, a.ctypes.data_as(C.POINTER(C.c_float)), int(flip)))
+
+
+# Defaults of the denoiser, chosen by the sweep of tools/denoise_probe.py (profiles/denoise_probe.json;
+# argued in DESIGN.md §5.7).  sigma_color=None means DENOISE_SIGMA_FACTOR x the median luminance of the
+# kept pixels' (demodulated) colour, computed on the host.
+DENOISE_DEFAULTS = {"iterations": 5, "sigma_plane": 0.005, "normal_power_log2": 3, "demodulate": True,
+                    "same_primitive": False}
+DENOISE_SIGMA_FACTOR = 4.0
+
+
+def _refuse(what: str) -> "PathtracerError":
+    return PathtracerError(N.PT_ERR_ARG, what)
+
+
+def denoise_params(iterations: int = 5, sigma_color: float = 1.0, sigma_plane: Optional[float] = None,
+                   normal_power_log2: Optional[int] = None, demodulate: Optional[bool] = None,
+                   same_primitive: Optional[bool] = None, staging: int = 0) -> "N.PtDenoiseParams":
+    """pt_denoise_params from keyword arguments, refused here (PT_ERR_ARG naming the field) before any
+    device call when a value is outside the accepted range of include/pt_hip.h."""
+    d = DENOISE_DEFAULTS
+    sigma_plane = d["sigma_plane"] if sigma_plane is None else sigma_plane
+    normal_power_log2 = d["normal_power_log2"] if normal_power_log2 is None else normal_power_log2
+    demodulate = d["demodulate"] if demodulate is None else demodulate
+    same_primitive = d["same_primitive"] if same_primitive is None else same_primitive
+    if int(iterations) != iterations or not 1 <= int(iterations) <= 8:
+        raise _refuse(f"denoise: iterations must be 1..8, not {iterations!r}")
+    sc, sp = np.float32(sigma_color), np.float32(sigma_plane)
+    if not (sc > 0 and np.isfinite(sc)):
+        raise _refuse(f"denoise: sigma_color must be > 0 and finite, not {sigma_color!r}")
+    if not (sp >= np.float32(1e-6) and np.isfinite(sp)):
+        raise _refuse(f"denoise: sigma_plane must be >= 1e-6 and finite, not {sigma_plane!r}")
+    if int(normal_power_log2) != normal_power_log2 or not 0 <= int(normal_power_log2) <= 7:
+        raise _refuse(f"denoise: normal_power_log2 must be 0..7, not {normal_power_log2!r}")
+    if staging not in (0, 1, 2):
+        raise _refuse(f"denoise: staging must be 0, 1 or 2, not {staging!r}")
+    flags = (N.PT_DENOISE_DEMODULATE if demodulate else 0) | (N.PT_DENOISE_SAME_PRIMITIVE if same_primitive else 0)
+    return N.PtDenoiseParams(int(iterations), float(sc), float(sp), int(normal_power_log2), flags, int(staging))
+
+
+def denoise_keep_mask(color: np.ndarray, plane1: np.ndarray, plane2: np.ndarray) -> np.ndarray:
+    """keep of the filter rule: HIT, not EMISSIVE, and colour, normal and position finite."""
+    fl = np.ascontiguousarray(plane2[..., 3]).view(np.uint32)
+    fin = np.isfinite(color[..., :3]).all(-1) & np.isfinite(plane1[..., :3]).all(-1) & np.isfinite(plane2[..., :3]).all(-1)
+    return ((fl & N.PT_FEATURE_HIT) != 0) & ((fl & N.PT_FEATURE_EMISSIVE) == 0) & fin
+
+
+def auto_sigma_color(color: np.ndarray, plane0: np.ndarray, plane1: np.ndarray, plane2: np.ndarray,
+                     demodulate: bool = True, factor: Optional[float] = None) -> float:
+    """The automatic sigma_color: `factor` (default DENOISE_SIGMA_FACTOR) x the median luminance of the kept
+    pixels' colour, divided by max(albedo, 1/64) first when demodulating.  1.0 when nothing is kept or the
+    median is not positive.  A host-side statistic: the device rule needs no reduction."""
+    keep = denoise_keep_mask(color, plane1, plane2)
+    if not keep.any():
+        return 1.0
+    c = color[..., :3][keep].astype(np.float32)
+    if demodulate:
+        c = c / np.maximum(plane0[..., :3][keep].astype(np.float32), np.float32(1.0 / 64.0))
+    lum = c @ np.array([0.2126, 0.7152, 0.0722], dtype=np.float32)
+    med = float(np.median(lum))
+    f = DENOISE_SIGMA_FACTOR if factor is None else float(factor)
+    return f * med if med > 0 and np.isfinite(med) else 1.0
+
+
+def _image4(name: str, a, shape=None) -> np.ndarray:
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4 or a.shape[0] == 0 or a.shape[1] == 0:
+        raise _refuse(f"denoise_image: {name} must be height x width x 4 float32, not shape {a.shape}")
+    if shape is not None and a.shape != shape:
+        raise _refuse(f"denoise_image: {name} has shape {a.shape}, color has {shape}")
+    return a
+
+
+def denoise_image(color, plane0, plane1, plane2, iterations: int = 5, sigma_color: Optional[float] = None,
+                  sigma_plane: Optional[float] = None, normal_power_log2: Optional[int] = None,
+                  demodulate: Optional[bool] = None, same_primitive: Optional[bool] = None, staging: int = 0,
+                  device: int = 0) -> np.ndarray:
+    """pt_denoise_image: the a-trous filter of include/pt_hip.h on host arrays (height x width x 4 float32:
+    the colour and the three feature planes of Pathtracer.features()["planes"]), without a Pathtracer --
+    for a frame gathered from several GPUs, or any image with such planes.  Returns height x width x 4."""
+    c = _image4("color", color)
+    planes = [_image4(f"plane{k}", p, c.shape) for k, p in enumerate((plane0, plane1, plane2))]
+    demod = DENOISE_DEFAULTS["demodulate"] if demodulate is None else demodulate
+    if sigma_color is None:
+        sigma_color = auto_sigma_color(c, *planes, demodulate=demod)
+    params = denoise_params(iterations, sigma_color, sigma_plane, normal_power_log2, demod, same_primitive, staging)
+    out = np.zeros_like(c)
+    fp = C.POINTER(C.c_float)
+    rc = N.hip().pt_denoise_image(int(device), c.shape[1], c.shape[0], c.ctypes.data_as(fp), planes[0].ctypes.data_as(fp),
+                                  planes[1].ctypes.data_as(fp), planes[2].ctypes.data_as(fp), C.byref(params),
+                                  out.ctypes.data_as(fp))
+    N.check_ctx(rc, None)
+    return out
 
 
 class Scene:
@@ -261,6 +354,76 @@ class Pathtracer:
             out = np.where(mean == 0, np.float32(0), se / np.abs(mean)).astype(np.float32)
         out[n < 2] = np.nan
         return out
+
+    # --- first-hit features and the denoiser (pt_render_features, pt_denoise; pt_hip.h) -------------
+    def features(self, camera: PtCamera) -> Dict[str, np.ndarray]:
+        """Trace each pixel's first-sample ray and return its closest hit (rows x width arrays): "albedo"
+        (x 3), "primitive" (uint32, 0xffffffff on a miss), "normal" (x 3, turned against the ray),
+        "depth" (the hit distance), "position" (x 3), "hit" and "emissive" (bool), and "planes": the three
+        raw float4 planes as denoise_image() takes them.  Touches nothing of the render state."""
+        self._single("features")
+        N.check_ctx(N.hip().pt_render_features(self._ctx, C.byref(camera)), self._ctx)
+        planes = []
+        for k in range(3):
+            p = np.zeros((self.rows, self.width, 4), dtype=np.float32)
+            N.check_ctx(N.hip().pt_read_features(self._ctx, k, p.ctypes.data_as(C.POINTER(C.c_float))), self._ctx)
+            planes.append(p)
+        flags = np.ascontiguousarray(planes[2][..., 3]).view(np.uint32)
+        self._planes = planes
+        return {"albedo": planes[0][..., :3].copy(), "primitive": np.ascontiguousarray(planes[0][..., 3]).view(np.uint32),
+                "normal": planes[1][..., :3].copy(), "depth": planes[1][..., 3].copy(),
+                "position": planes[2][..., :3].copy(), "hit": (flags & N.PT_FEATURE_HIT) != 0,
+                "emissive": (flags & N.PT_FEATURE_EMISSIVE) != 0, "planes": planes}
+
+    def denoise(self, iterations: int = 5, sigma_color: Optional[float] = None, sigma_plane: Optional[float] = None,
+                normal_power_log2: Optional[int] = None, demodulate: Optional[bool] = None,
+                same_primitive: Optional[bool] = None, staging: int = 0, frames: Optional[int] = None) -> np.ndarray:
+        """Filter the image with the edge-avoiding a-trous denoiser (include/pt_hip.h), guided by the
+        planes of the last features(camera) call; returns rows x width x 4 float32 in
+        get_hdr_image_data()'s units and leaves the accumulation as it is.  sigma_color=None: a factor times
+        the median luminance of the kept pixels (auto_sigma_color).  `frames`: the divisor of the
+        accumulation (default: the frame counter; an adaptive render divides every pixel by its own count).
+        Arguments out of range raise before any device call."""
+        self._single("denoise")
+        demod = DENOISE_DEFAULTS["demodulate"] if demodulate is None else demodulate
+        params = denoise_params(iterations, 1.0 if sigma_color is None else sigma_color, sigma_plane, normal_power_log2,
+                                demod, same_primitive, staging)
+        f = self.frames if frames is None else int(frames)
+        if sigma_color is None:
+            planes = getattr(self, "_planes", None)
+            if planes is None:
+                raise PathtracerError(N.PT_ERR_STATE, "denoise: no feature planes (call features(camera) first)")
+            if self.adaptive:
+                color = self.get_hdr_image_data()
+            else:
+                color = self.accum() * (np.float32(1.0) / np.float32(max(f, 1)))
+            params.sigma_color = auto_sigma_color(color, *planes, demodulate=demod)
+        N.check_ctx(N.hip().pt_denoise(self._ctx, f, C.byref(params)), self._ctx)
+        return self.denoised()
+
+    def denoised(self) -> np.ndarray:
+        """The last denoise()'s result again (pt_read_denoised)."""
+        self._single("denoised")
+        out = np.zeros((self.rows, self.width, 4), dtype=np.float32)
+        N.check_ctx(N.hip().pt_read_denoised(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float))), self._ctx)
+        return out
+
+    def tonemap_denoised(self) -> np.ndarray:
+        """The last denoise()'s result through the tonemap (RGBA8, rows x width)."""
+        self._single("tonemap_denoised")
+        out = np.zeros((self.rows, self.width, 4), dtype=np.uint8)
+        N.check_ctx(N.hip().pt_tonemap_denoised(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint8))), self._ctx)
+        return out
+
+    def denoise_timing(self) -> Dict[str, object]:
+        """Kernel times of the last features() and denoise() in ms: {"features", "prepare", "iterations", "finish"}."""
+        self._single("denoise_timing")
+        ms = (C.c_float * 10)()
+        fm = C.c_float(0.0)
+        N.check_ctx(N.hip().pt_read_denoise_timing(self._ctx, ms), self._ctx)
+        N.check_ctx(N.hip().pt_read_features_timing(self._ctx, C.byref(fm)), self._ctx)
+        return {"features": float(fm.value), "prepare": float(ms[0]), "iterations": [float(x) for x in ms[1:9]],
+                "finish": float(ms[9])}
 
     def get_timing(self) -> float:
         return float(N.host().pth_renderer_timing(self._r))

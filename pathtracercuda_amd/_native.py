@@ -61,6 +61,17 @@ class PtAdaptiveResult(C.Structure):
     _fields_ = [("rounds", C.c_uint32), ("samples", C.c_uint64), ("gpu_ms", C.c_float)]
 
 
+class PtDenoiseParams(C.Structure):
+    """pt_denoise_params (pt_hip.h, a-trous denoiser)."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_plane", C.c_float),
+                ("normal_power_log2", C.c_uint32), ("flags", C.c_uint32), ("staging", C.c_uint32)]
+
+
+PT_FEATURE_HIT, PT_FEATURE_EMISSIVE = 1, 2
+PT_DENOISE_DEMODULATE, PT_DENOISE_SAME_PRIMITIVE = 1, 2
+PT_DENOISE_TILE_W, PT_DENOISE_TILE_H = 32, 8
+
+
 # symbol -> (restype, argtypes); the CPU test suite checks that every declaration in include/*.h
 # is exported and bound here.
 P = C.POINTER
@@ -112,6 +123,15 @@ _HIP_SYMBOLS = {
     "pt_read_group_fold": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint32)]),
     "pt_read_group_log_counts": (C.c_int, [C.c_void_p, P(C.c_uint32), C.c_size_t]),
     "pt_last_error": (C.c_char_p, [C.c_void_p]),
+    "pt_render_features": (C.c_int, [C.c_void_p, P(PtCamera)]),
+    "pt_read_features": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_float)]),
+    "pt_read_features_timing": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_denoise": (C.c_int, [C.c_void_p, C.c_uint32, P(PtDenoiseParams)]),
+    "pt_read_denoise_timing": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_read_denoised": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_tonemap_denoised": (C.c_int, [C.c_void_p, P(C.c_uint8)]),
+    "pt_denoise_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, P(C.c_float), P(C.c_float), P(C.c_float),
+                                   P(C.c_float), P(PtDenoiseParams), P(C.c_float)]),
     "pt_group_create": (C.c_int, [C.c_int, P(C.c_int), C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_void_p)]),
     "pt_group_destroy": (None, [C.c_void_p]),
     "pt_group_size": (C.c_int, [C.c_void_p]),
@@ -155,6 +175,10 @@ _HOST_SYMBOLS = {
     "pth_renderer_render": (C.c_int, [C.c_void_p, P(PtCamera), C.c_uint32, C.c_uint32, C.c_int]),
     "pth_renderer_render_adaptive": (C.c_int, [C.c_void_p, P(PtCamera), P(PtAdaptiveParams), P(PtAdaptiveResult)]),
     "pth_renderer_adaptive": (C.c_int, [C.c_void_p]),
+    "pth_renderer_features": (C.c_int, [C.c_void_p, P(PtCamera)]),
+    "pth_renderer_feature_plane": (P(C.c_float), [C.c_void_p, C.c_uint32]),
+    "pth_renderer_denoise": (C.c_int, [C.c_void_p, P(PtDenoiseParams), C.c_int, P(C.c_float)]),
+    "pth_renderer_denoised": (C.c_int, [C.c_void_p]),
     "pth_renderer_timing": (C.c_float, [C.c_void_p]),
     "pth_renderer_frames": (C.c_uint32, [C.c_void_p]),
     "pth_renderer_local_rows": (C.c_uint32, [C.c_void_p]),

@@ -10,6 +10,9 @@
 //                  until the standard error of the pixel's luminance is below T x (|mean| + 0.01);
 //                  -spp is the budget (at most spp / chunk calls), -minspp N the samples every pixel
 //                  gets (default two calls).  One GPU.
+//   -denoise [N]   filter the image before -o / -ohdr write it: the edge-avoiding a-trous denoiser guided
+//                  by the first-hit feature buffers (Pathtracer::renderFeatures + denoise), N = 1..8
+//                  iterations (default 5), the other parameters at their defaults.  One GPU.
 // The windowed / interactive mode (-window, -enable_controls) is not supported.
 #include <algorithm>
 #include <cstdio>
@@ -75,13 +78,31 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
             i += 2;
             continue;
         }
+        if (strcmp(argv[i], "-denoise") == 0) {
+            // the iteration count is optional: the next argument is taken as it unless it is another
+            // option or the input file (the last argument)
+            params.m_denoise = PT_DENOISE_DEFAULT_ITERATIONS;
+            if (i + 2 < argc && argv[i + 1][0] != '-') {
+                char* end = nullptr;
+                const long n = strtol(argv[i + 1], &end, 10);
+                if (end == argv[i + 1] || *end != '\0' || n < 1 || n > 8) {
+                    printf("Invalid input for -denoise! (1..8 iterations)\n");
+                    displayHelp = true;
+                } else params.m_denoise = (unsigned int)n;
+                i += 2;
+            } else ++i;
+            continue;
+        }
         if (strcmp(argv[i], "-minspp") == 0) { uintArg(i, "-minspp", params.m_minSpp); i += 2; continue; }
         printf("Can't parse argument: %s\n", argv[i]);
         displayHelp = true;
         break;
     }
-    if (i < argc && argc > 1) params.m_inputFilepath = argv[argc - 1];
-    else if (!(argc == 2 && strcmp(argv[1], helpOption) == 0)) {
+    // (`pathtracer -help` alone lists the options: the lone argument is not an input file)
+    const bool helpOnly = argc == 2 && strcmp(argv[1], helpOption) == 0;
+    if (helpOnly) displayHelp = true;
+    else if (i < argc && argc > 1) params.m_inputFilepath = argv[argc - 1];
+    else {
         printf("Missing input file argument!\n");
         displayHelp = true;
     }
@@ -101,6 +122,8 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
         printf("%-30s One kernel launch per render() call (default: all calls in one launch)\n", "-call_loop");
         printf("%-30s Adaptive sampling to this relative noise tolerance; -spp is the budget\n", "-adaptive");
         printf("%-30s Samples every pixel gets with -adaptive (default two calls)\n", "-minspp");
+        printf("%-30s Denoise before writing: a-trous filter guided by first-hit features, N = 1..8 iterations (default 5)\n",
+               "-denoise [N]");
         return false;
     }
     params.m_enableControls = params.m_enableControls && params.m_showWindow;
@@ -135,6 +158,10 @@ int main(int argc, char* argv[])
     }
     gpus = std::max(1, std::min(gpus, available));
     const bool adaptive = params.m_adaptive >= 0.0f;
+    if (params.m_denoise && gpus > 1) {
+        printf("-denoise renders on one GPU; ignoring -gpus.\n");
+        gpus = 1;
+    }
     if (adaptive && gpus > 1) {
         printf("-adaptive renders on one GPU; ignoring -gpus.\n");
         gpus = 1;
@@ -179,6 +206,14 @@ int main(int argc, char* argv[])
         }
     }
     if (!adaptive) printf("Finished accumulating %d samples in %f ms GPU time\n", (int)params.m_spp, totalGpuTime);
+
+    if (params.m_denoise) {
+        Pathtracer::DenoiseOptions options;
+        options.iterations = params.m_denoise;
+        pathtracer->renderFeatures(camera);
+        const float sigma = pathtracer->denoise(options);
+        printf("Denoised: %u a-trous iterations, colour sigma %g\n", options.iterations, sigma);
+    }
 
     if (params.m_outputFilepath) {
         printf("Writing result to %s\n", params.m_outputFilepath);

@@ -301,6 +301,43 @@ PT_API int pth_renderer_render_adaptive(pth_renderer* r, const pt_camera* camera
 
 PT_API int pth_renderer_adaptive(const pth_renderer* r) { return r && r->pt->adaptive() ? 1 : 0; }
 
+PT_API int pth_renderer_features(pth_renderer* r, const pt_camera* camera)
+{
+    if (!r || !camera) return setError(PT_ERR_ARG, "invalid argument");
+    PTH_GUARD_BEGIN
+    r->pt->renderFeatures(camera_from_device(*camera));
+    return PT_OK;
+    PTH_GUARD_END
+}
+
+PT_API const float* pth_renderer_feature_plane(pth_renderer* r, uint32_t plane)
+{
+    if (!r) return nullptr;
+    ptamd::g_throwOnError = true;
+    try { return r->pt->featurePlane(plane); } catch (const std::exception& e) { setError(PT_ERR_STATE, e.what()); }
+    return nullptr;
+}
+
+PT_API int pth_renderer_denoise(pth_renderer* r, const pt_denoise_params* params, int auto_sigma, float* sigma_used)
+{
+    if (!r || !params) return setError(PT_ERR_ARG, "invalid argument");
+    if (!auto_sigma && !(params->sigma_color > 0.0f)) return setError(PT_ERR_ARG, "pth_renderer_denoise: sigma_color must be > 0");
+    PTH_GUARD_BEGIN
+    Pathtracer::DenoiseOptions o;
+    o.iterations = params->iterations;
+    o.sigmaColor = auto_sigma ? 0.0f : params->sigma_color;
+    o.sigmaPlane = params->sigma_plane;
+    o.normalPowerLog2 = params->normal_power_log2;
+    o.flags = params->flags;
+    o.staging = params->staging;
+    const float used = r->pt->denoise(o);
+    if (sigma_used) *sigma_used = used;
+    return PT_OK;
+    PTH_GUARD_END
+}
+
+PT_API int pth_renderer_denoised(const pth_renderer* r) { return r && r->pt->denoised() ? 1 : 0; }
+
 PT_API float pth_renderer_timing(const pth_renderer* r) { return r ? r->pt->getTiming() : 0.0f; }
 PT_API uint32_t pth_renderer_frames(const pth_renderer* r) { return r ? r->pt->accumulatedFrames() : 0; }
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer* r) { return r ? r->pt->localRows() : 0; }

@@ -2,10 +2,13 @@
 // Host side keeps the reference's responsibilities: BVH build + validation on setScene, texture
 // decode on loadTexture, the accumulated-frame counter and the two normalisations of
 // getHDRImageData / getImageData.  Device work goes through the C ABI of include/pt_hip.h.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
+#include <vector>
 
 #include "host_internal.h"
 #include "pathtracer_amd.hpp"
@@ -96,6 +99,7 @@ void Pathtracer::setScene(size_t count, const CpuHittable* hittables)
         check(pt_set_scene(m_ctx, dn.data(), (uint32_t)dn.size(), dp.data(), (uint32_t)dp.size()), "pt_set_scene");
     m_nodeCount = (uint32_t)dn.size();
     m_hittableCount = (uint32_t)dp.size();
+    m_denoised = false;
 }
 
 void Pathtracer::render(const Camera& camera, uint32_t spp, bool ignoreHistory)
@@ -111,6 +115,7 @@ void Pathtracer::renderChunks(const Camera& camera, uint32_t spp, uint32_t chunk
         check(PT_ERR_STATE, "render: the buffer holds an adaptive render; continue it with renderAdaptive(reset = false) "
                             "or start over with ignoreHistory");
     m_adaptive = false;
+    m_denoised = false;
     if (ignoreHistory) m_accumulatedFrames = 0;
     m_timing = 0.0f;
     const pt_camera cam = camera.toDevice();
@@ -133,8 +138,63 @@ Pathtracer::AdaptiveResult Pathtracer::renderAdaptive(const Camera& camera, uint
     check(pt_render_adaptive(m_ctx, &cam, &ap, &res), "pt_render_adaptive");
     m_timing = res.gpu_ms;
     m_adaptive = true;
+    m_denoised = false;
     m_accumulatedFrames = 0;          // the per-pixel counts describe the buffer now
     return AdaptiveResult{res.rounds, res.samples, res.gpu_ms};
+}
+
+void Pathtracer::renderFeatures(const Camera& camera)
+{
+    if (m_group) check(PT_ERR_STATE, "renderFeatures: not available on a device group");
+    const pt_camera cam = camera.toDevice();
+    check(pt_render_features(m_ctx, &cam), "pt_render_features");
+}
+
+const float* Pathtracer::featurePlane(uint32_t plane)
+{
+    if (m_group) check(PT_ERR_STATE, "featurePlane: not available on a device group");
+    m_featureBuffer.resize((size_t)localRows() * m_width * 4);
+    check(pt_read_features(m_ctx, plane, m_featureBuffer.data()), "pt_read_features");
+    return m_featureBuffer.data();
+}
+
+float Pathtracer::denoise(const DenoiseOptions& o)
+{
+    if (m_group) check(PT_ERR_STATE, "denoise: not available on a device group");
+    pt_denoise_params p = {o.iterations, o.sigmaColor, o.sigmaPlane, o.normalPowerLog2, o.flags, o.staging};
+    if (!(o.sigmaColor > 0.0f)) {
+        // automatic: a factor times the median luminance of the kept pixels' (demodulated) colour
+        const size_t npix = (size_t)localRows() * m_width;
+        m_denoised = false;
+        const float* c = getHDRImageData();
+        std::vector<float> a(npix * 4), n(npix * 4), q(npix * 4), lum;
+        check(pt_read_features(m_ctx, 0, a.data()), "pt_read_features");
+        check(pt_read_features(m_ctx, 1, n.data()), "pt_read_features");
+        check(pt_read_features(m_ctx, 2, q.data()), "pt_read_features");
+        lum.reserve(npix);
+        for (size_t i = 0; i < npix; ++i) {
+            uint32_t fl;
+            memcpy(&fl, &q[4 * i + 3], 4);
+            bool keep = (fl & PT_FEATURE_HIT) && !(fl & PT_FEATURE_EMISSIVE);
+            float v[3];
+            for (int k = 0; k < 3; ++k) {
+                keep = keep && std::isfinite(c[4 * i + k]) && std::isfinite(n[4 * i + k]) && std::isfinite(q[4 * i + k]);
+                const float d = (o.flags & PT_DENOISE_DEMODULATE) ? fmaxf(a[4 * i + k], 1.0f / 64.0f) : 1.0f;
+                v[k] = c[4 * i + k] / d;
+            }
+            if (keep) lum.push_back((0.2126f * v[0] + 0.7152f * v[1]) + 0.0722f * v[2]);
+        }
+        p.sigma_color = 1.0f;
+        if (!lum.empty()) {
+            std::sort(lum.begin(), lum.end());
+            const size_t h = lum.size() / 2;
+            const float med = (lum.size() & 1) ? lum[h] : 0.5f * (lum[h - 1] + lum[h]);
+            if (med > 0.0f && std::isfinite(med)) p.sigma_color = PT_DENOISE_DEFAULT_SIGMA_FACTOR * med;
+        }
+    }
+    check(pt_denoise(m_ctx, m_accumulatedFrames, &p), "pt_denoise");
+    m_denoised = true;
+    return p.sigma_color;
 }
 
 float Pathtracer::getTiming() const { return m_timing; }
@@ -161,7 +221,11 @@ void Pathtracer::setSkyboxTextureHandle(uint32_t handle)
 
 float* Pathtracer::getHDRImageData()
 {
-    if (m_adaptive) {                  // every pixel over its own number of calls
+    if (m_denoised) {
+        check(pt_read_denoised(m_ctx, m_cpuAccumBuffer.data()), "pt_read_denoised");
+        return m_cpuAccumBuffer.data();
+    }
+    if (m_adaptive) {                 // every pixel over its own number of calls
         check(pt_read_adaptive_hdr(m_ctx, m_cpuAccumBuffer.data()), "pt_read_adaptive_hdr");
         return m_cpuAccumBuffer.data();
     }
@@ -178,6 +242,10 @@ float* Pathtracer::getHDRImageData()
 
 char* Pathtracer::getImageData()
 {
+    if (m_denoised) {
+        check(pt_tonemap_denoised(m_ctx, (uint8_t*)m_cpuResultBuffer.data()), "pt_tonemap_denoised");
+        return m_cpuResultBuffer.data();
+    }
     if (m_adaptive) {
         check(pt_tonemap_adaptive(m_ctx, (uint8_t*)m_cpuResultBuffer.data()), "pt_tonemap_adaptive");
         return m_cpuResultBuffer.data();

@@ -455,6 +455,8 @@ __global__ void __launch_bounds__(256) adapt_scatter_kernel(const unsigned long 
 
 #include "pt_dev_fold.h"
 
+#include "pt_dev_denoise.h"
+
 // Multi-device gather, second half: scatter one device's received rows (its bands, in local row
 // order) into the full image.  A band is band-rows consecutive image rows in both buffers, so every
 // lane copies one float4 of a coalesced row.
@@ -569,6 +571,14 @@ struct pt_context {
     uint32_t* adList = nullptr;       // [pixels] active local pixel indices, tile-major
     void* adTemp = nullptr;
     size_t adTempBytes = 0;
+    // first-hit feature planes and the denoiser (pt_denoise.h); no render state
+    float4* feat = nullptr;           // [3][pixels], allocated by the first pt_render_features
+    bool featValid = false;           // the planes describe the current scene and textures
+    float featMs = 0.0f;
+    float4* dnBuf = nullptr;          // [6][pixels]: colour, two guide planes, two iteration buffers, the result
+    bool dnValid = false;             // dnBuf holds a denoised image
+    hipEvent_t dnEv[12] = {};
+    float dnMs[10] = {};
     pt_camera lastCam = {};
     uint64_t epoch = 0;           // launches that wrote the accumulation (a group's gather cache key)
     std::string err;
@@ -1029,6 +1039,10 @@ PT_API void pt_destroy(pt_context* ctx)
     (void)hipFree(ctx->adOffsets);
     (void)hipFree(ctx->adList);
     (void)hipFree(ctx->adTemp);
+    (void)hipFree(ctx->feat);
+    (void)hipFree(ctx->dnBuf);
+    for (auto& e : ctx->dnEv)
+        if (e) (void)hipEventDestroy(e);
     for (auto& t : ctx->hostTex) (void)hipFree((void*)t.texels);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -1186,6 +1200,7 @@ PT_API int pt_set_scene(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node
     ctx->dfsOrder = dfsOrder;
     ctx->orderStale = true;
     ctx->adMomValid = false;
+    ctx->featValid = false;
     ++ctx->stateEpoch;
     ctx->rootWord = word(0);
     for (int k = 0; k < 3; ++k) {
@@ -1246,6 +1261,7 @@ PT_API int pt_set_texture(pt_context* ctx, uint32_t handle, const float* rgba, u
     t.fheight = (float)height;
     ctx->orderStale = true;
     ctx->adMomValid = false;
+    ctx->featValid = false;
     ++ctx->stateEpoch;
     PT_HIP_CHECK(ctx, hipMemcpy(ctx->texTable, ctx->hostTex, sizeof(ctx->hostTex), hipMemcpyHostToDevice));
     return PT_OK;
@@ -2297,8 +2313,14 @@ PT_API int pt_set_kernel_variant(pt_context* ctx, int variant)
     return PT_OK;
 }
 
-PT_API const char* pt_last_error(const pt_context* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
-
 } // extern "C"
+
+#include "pt_denoise.h"
+
+extern "C" PT_API const char* pt_last_error(const pt_context* ctx)
+{
+    if (ctx) return ctx->err.c_str();
+    return g_freeError.empty() ? "null context" : g_freeError.c_str();
+}
 
 #include "pt_group.h"
