@@ -5,6 +5,7 @@
 #   pathtracercuda_amd/lib/fp_exhaustive  all-inputs check of the kernel's fast 1/x and sqrt (GPU)
 #   pathtracercuda_amd/lib/host_sanitize_check  ASan/UBSan mutation check of the host parsers (CPU)
 #   pathtracercuda_amd/lib/leaf_forms_check  exact vs fast form of the cube leaf test (CPU; `make leafcheck` runs it)
+#   pathtracercuda_amd/lib/launch_plan_check  the launch policy and the build table on the host, for tests/test_launch_plan.py (CPU)
 #   oracle/liboracle.so                   CPU restatement (test infrastructure only)
 #   oracle/_ref/libptref.so               the reference's own source built for the host, when a checkout
 #                                         of it is at $(REF) (test infrastructure only; oracle/Makefile)
@@ -30,7 +31,7 @@ HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fno-slp-vec
 CXXFLAGS ?= -O2 -std=c++17 -ffp-contract=off -fno-fast-math -fPIC -Iinclude -I$(SRC)/host -Wall -Wextra \
             -Wno-unused-parameter -Wno-missing-field-initializers
 
-all: $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer $(LIB)/fp_exhaustive $(LIB)/host_sanitize_check $(LIB)/leaf_forms_check oracle
+all: $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer $(LIB)/fp_exhaustive $(LIB)/host_sanitize_check $(LIB)/leaf_forms_check $(LIB)/launch_plan_check oracle
 
 $(LIB):
 	mkdir -p $(LIB)
@@ -66,6 +67,12 @@ $(LIB)/leaf_forms_check: tools/leaf_forms_check.cpp $(SRC)/pt_leaf_forms.h | $(L
 	  -o $@ tools/leaf_forms_check.cpp
 leafcheck: $(LIB)/leaf_forms_check
 	$(LIB)/leaf_forms_check
+
+# Host view of the launch policy (csrc/pt_launch_plan.h, csrc/pt_builds.h) under ASan/UBSan; run by
+# tests/test_launch_plan.py.
+$(LIB)/launch_plan_check: tools/launch_plan_check.cpp $(SRC)/pt_launch_plan.h $(SRC)/pt_builds.h | $(LIB)
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	  -o $@ tools/launch_plan_check.cpp
 
 clean:
 	rm -f $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer

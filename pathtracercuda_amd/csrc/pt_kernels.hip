@@ -34,9 +34,11 @@
 #include <atomic>
 #include <thread>
 #include <chrono>
+#include <utility>
 
 #include "pt_math.h"
 #include "pt_leaf_forms.h"
+#include "pt_launch_plan.h"
 #include "../../include/pt_hip.h"
 
 using namespace pt;
@@ -478,6 +480,7 @@ __global__ void __launch_bounds__(256) unpermute_rows_kernel(float4* __restrict_
 // =============================================================================================
 struct pt_context {
     int device = 0;
+    int cus = 0;                      // compute units of the device
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint32_t width = 0, height = 0, rowOffset = 0, rowStride = 1, rows = 0, bandShift = 0;
@@ -489,7 +492,6 @@ struct pt_context {
     float4* cnodes = nullptr;   // child-box records (traverse_cb); null when the scene exceeds its encoding
     uint32_t cnodeCount = 0, rootWord = 0;
     bool dfsOrder = true;             // leaves hold their primitives in DFS order (repair_pending)
-    bool riseRepair = true;           // pt_set_rise_repair (tests' negative control only)
     int zeroConstsType = -1;          // pt_set_zero_quadric_consts (tests' negative control only)
     // run-ahead across render() calls (MODE 4): the stash and the key it was made under
     uint32_t* ahead = nullptr;        // [kAheadWords][pixels]
@@ -497,17 +499,13 @@ struct pt_context {
     pt_camera aheadCam = {};
     uint64_t aheadState = 0;          // stateEpoch when it was made
     uint32_t aheadMisses = 0;         // consecutive launches that could not use the previous stash
-    int aheadMode = 0;                // pt_set_run_ahead: 0 automatic, 1 off, 2 always make a stash, 3 make but never use
-    uint32_t prepassSpp = 0;          // pt_set_cold_start: 0 = first call split off (pre-pass of kPrepassSpp for
-                                      // one-call launches), > 0 = a discarded pre-pass of that many spp
-    bool coldPriority = true;         // pt_set_cold_start: issue priority on the cold start's order
     uint64_t stateEpoch = 0;          // bumped by every change of scene, textures, sky or RNG state
     uint64_t lastState = 0;           // stateEpoch at the last launch
     bool launched = false;
     float rootBox[6] = {};
     uint32_t nodeCount = 0, primCount = 0, stackDepth = 1;
     bool slabFast = true;
-    int variant = 0;
+    LaunchKnobs knobs;                // pt_set_* (pt_launch_plan.h)
     uint32_t lastLaunch[4] = {};      // pt_last_launch: LDS bytes, staging level, waves per workgroup, workgroups
     DevTex* texTable = nullptr;
     DevTex hostTex[PT_MAX_TEXTURES] = {};
@@ -528,19 +526,11 @@ struct pt_context {
     size_t sortTempBytes = 0;
     uchar4* ldr = nullptr;        // tonemap staging buffer (pt_tonemap)
     uint32_t orderTiles = 0;      // tiles the device buffers hold
-    bool orderValid = false;      // `order` holds a cost-sorted permutation
-    bool orderStale = true;       // rebuild it after the next launch (scene, texture or camera changed)
-    uint64_t orderSamples = 0;    // samples per pixel of the launch whose tile costs built `order`
-    int schedule = 0;             // 0 = cost-sorted tiles (default), 1 = row-major
-    int stripMode = 0;            // strip units: 0 = automatic, 1 = off, K >= 2 = always K tiles per unit
-    uint32_t orderStrip = 1;      // tiles per unit of the launch whose costs built `order`
+    OrderState orderState;        // of `order` (pt_launch_plan.h)
     uint32_t* unitMajor = nullptr;    // row-major order of strip units (packed first tiles), for unitK
     uint32_t unitK = 0, unitTiles = 0;
     uint32_t occupancy = 0;       // tuning knob: workgroups per CU of persistent grids (0 = all that fit)
-    int prioMode = 0;             // issue priority: 0 = automatic, 1 = off, 2 = explicit bounds prioBounds
-    uint32_t prioBounds[3] = {0, 0, 0};
     // speculative sample groups
-    int ssgMode = 0;              // 0 = automatic, 1 = off, G >= 2 = always G groups (tests)
     uint32_t patchRounds = 6;     // patch rounds before the remaining dead ends run plain
     uint32_t ssgLook[2] = {64, 16}; // second-phase lag tolerances in samples (TraceParams::ssgLook)
     float* pairs = nullptr;       // per-pixel draw pairs per sample (start-offset guesses)
@@ -584,14 +574,14 @@ struct pt_context {
     std::string err;
 };
 
-#define PT_HIP_CHECK(ctx, expr)                                                              \
+#define PT_HIP_CHECK(ctx, ...)                                                               \
     do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
+        hipError_t e_ = (__VA_ARGS__);                                                         \
         if (e_ != hipSuccess) {                                                              \
             if (ctx) {                                                                       \
                 char b_[512];                                                                \
                 snprintf(b_, sizeof(b_), "HIP error = %u (%s) at %s:%d '%s'", (unsigned)e_,  \
-                         hipGetErrorString(e_), __FILE__, __LINE__, #expr);                  \
+                         hipGetErrorString(e_), __FILE__, __LINE__, #__VA_ARGS__);           \
                 (ctx)->err = b_;                                                             \
             }                                                                                \
             return PT_ERR_HIP;                                                               \
@@ -626,22 +616,22 @@ static inline void note_launch(size_t lds, int sl, int wpb, unsigned groups)
     g_lastLaunch[3] = groups;
 }
 
-// Kernel variants (workgroup size, scene staged in LDS or read through the caches).
+// One instantiation of trace_kernel on a device of `cus` compute units, and its fallbacks: no
+// child-box layout -> the node-at-a-time walk, too large to stage -> the scene through the caches, a
+// grid that fits in one pass -> the plain (non-persistent) kernel.
 template <bool STATS, int SL, int WPB, int WW, int MINW, bool PERSIST = false, int MODE = 0>
-static hipError_t launch_one(const TraceParams& P, hipStream_t stream)
+static hipError_t launch_one(const TraceParams& P, int cus, hipStream_t stream)
 {
-    const size_t nodeF4 = WW >= 3 ? 4 * (size_t)P.cnodeCount : 2 * (size_t)P.nodeCount;
-    const size_t sceneBytes = ((SL >= 1 ? nodeF4 : 0) + (SL >= 2 ? 4 * (size_t)P.primCount : 0)) * sizeof(float4);
-    const size_t lds = sceneBytes + (size_t)WPB * P.stackDepth * 64 * (WW >= 3 ? 8 : 4) + (size_t)WPB * 64 * 12;
+    const size_t lds = lds_bytes(SL, WPB, WW >= 3, SceneSize{P.nodeCount, P.cnodeCount, P.primCount, P.stackDepth});
     // no child-box layout: the node-at-a-time walk -- except for grouped and strip launches, whose
-    // item and strip hand-off logic lives only in the resumable walk (pick_variant never sends them here)
+    // item and strip hand-off logic lives only in the resumable walk (picked_build never sends them here)
     if (WW >= 3 && P.cnodes == nullptr) {
         if constexpr (MODE == 1 || MODE >= 3) return hipErrorInvalidValue;
-        else return launch_one<STATS, SL, WPB, 1, MINW, PERSIST, MODE>(P, stream);
+        else return launch_one<STATS, SL, WPB, 1, MINW, PERSIST, MODE>(P, cus, stream);
     }
-    if (lds > 160 * 1024) {
+    if (lds > kLdsLimit) {
         // scene too large to stage in LDS: the same variant reading the scene through the caches
-        if (SL > 0) return launch_one<STATS, 0, WPB, WW, MINW, PERSIST, MODE>(P, stream);
+        if (SL > 0) return launch_one<STATS, 0, WPB, WW, MINW, PERSIST, MODE>(P, cus, stream);
         return hipErrorInvalidValue;                   // the stacks alone exceed the LDS
     }
     // the dynamic-LDS limit is raised once per device (contexts on several devices may run on
@@ -652,7 +642,7 @@ static hipError_t launch_one(const TraceParams& P, hipStream_t stream)
     const uint64_t bit = 1ull << (dev & 63);
     if (!(attrSet.load() & bit)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_kernel<STATS, SL, WPB, WW, MINW, PERSIST, MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
         if (e != hipSuccess) return e;
         attrSet.fetch_or(bit);
     }
@@ -663,21 +653,15 @@ static hipError_t launch_one(const TraceParams& P, hipStream_t stream)
         static std::atomic<int> resident[64];
         int cap = resident[dev & 63].load();
         if (cap == 0) {
-            int cus = 0, perCu = 0;
-            hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            if (e == hipSuccess)
-                e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                    &perCu, reinterpret_cast<const void*>(&trace_kernel<STATS, SL, WPB, WW, MINW, PERSIST, MODE>), WPB * 64, lds);
+            int perCu = 0;
+            hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                &perCu, reinterpret_cast<const void*>(&trace_kernel<STATS, SL, WPB, WW, MINW, PERSIST, MODE>), WPB * 64, lds);
             if (e != hipSuccess) return e;
-            cap = std::max(cus, 1) * std::max(perCu, 1);
+            cap = cus * std::max(perCu, 1);
             resident[dev & 63].store(cap);
         }
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-        if (P.occCap && cus > 0)                       // tuning knob (pt_set_occupancy): fewer waves per SIMD
+        if (P.occCap)                                  // tuning knob (pt_set_occupancy): fewer waves per SIMD
             cap = cus * std::min(cap / cus, (int)P.occCap);
-        else if (P.occCap)
-            cap = 0;
         if constexpr (MODE == 5) {
             // adaptive rounds shrink from launch to launch: a list that fits in one pass runs the same
             // kernel on a grid of its own size, every wave taking its slot from the cursor (one build
@@ -688,11 +672,11 @@ static hipError_t launch_one(const TraceParams& P, hipStream_t stream)
                 return hipGetLastError();
             }
         } else {
-            if (!P.occCap && blocks <= (unsigned)cap) return launch_one<STATS, SL, WPB, WW, MINW, false, MODE>(P, stream);
+            if (!P.occCap && blocks <= (unsigned)cap) return launch_one<STATS, SL, WPB, WW, MINW, false, MODE>(P, cus, stream);
         }
         if (cap <= 0) return hipErrorInvalidValue;
         TraceParams Q = P;                             // first slots dealt per SIMD (spread_slot)
-        Q.spreadCU = (cus > 0 && WPB % 4 == 0 && cap % cus == 0) ? (uint32_t)cus : 0u;
+        Q.spreadCU = (WPB % 4 == 0 && cap % cus == 0) ? (uint32_t)cus : 0u;
         if (P.prioDealt) {
             // Every position dealt at the start runs in the first priority band.  Waves of equal
             // priority issue oldest first (the resident grid's dispatch order: tools/tile_trace.py shows
@@ -714,190 +698,38 @@ static hipError_t launch_one(const TraceParams& P, hipStream_t stream)
     return hipGetLastError();
 }
 
-// Shipped variants (all bit-identical).  Measured-and-rejected variants of earlier rounds (single
-// loop with LDS nodes, other exit thresholds, 2/8/16-wave groups, 6-8 waves/SIMD, speculative
-// traversal, select-form primitive tests, a ballot-driven phase scheduler) are recorded in DESIGN.md
-// and git history, not shipped.
-//   1   reference control flow (one loop, node at a time), scene read through the caches
-//   4   node-at-a-time while-while, caches, 5 waves/SIMD   (scenes outside the child-box encoding)
-//   6   node-at-a-time while-while, nodes in LDS           (idem, small BVH)
-//   20  child-box traversal, one tile per wave             (counts the reference's node/prim tests)
-// The WW parameter of the resumable walk encodes 100000 * NOREPAIR + 10000 * SKYQ + 1000 * DEFERQ + 200 + EXITQ
-// (deferred shading and the traversal's exit threshold, see trace_kernel).
-//   39  variant 40 without deferred shading, exit <= 24/64 (the round-1 default; A/B reference)
-//   40  default: resumable lean child-box walk, records in LDS, persistent waves, deferred shading
-//       (hits >= 4/8, misses >= 1/8 with a sky texture), exit <= 12/64
-//   41  default for cache-read scenes: same, records through the caches
-//   46  default for deep cache-read BVHs: variant 41 compiled for 4 waves/SIMD (128 VGPRs)
-//   47  small grids (<= 4 tiles per SIMD): variant 39 compiled for 4 waves/SIMD (128 VGPRs); no
-//       deferral, which costs a single pass of latency-bound waves 2.8 %
-//   48  small grids whose primitives fit in LDS too: records and primitives in LDS, 4 waves/SIMD,
-//       deferred hits
-// Variants 50/51 (leaf tests compacted across a round's lanes by shape family, -14.6 % on C3) were
-// measured in round 3 and removed in round 4; commit 1b0d322 has them.
-constexpr int kV40Walk = 14212;     // variant 40's walk parameters (SKYQ 1, DEFERQ 4, exit <= 12/64;
-                                    // retuned in round 3, profiles/r03_walk_params_ab.json)
-template <bool STATS, int MODE = 0>
-static hipError_t launch_variant(int v, const TraceParams& P, hipStream_t stream)
+// Launch build `v` (pt_builds.h) in launch mode (STATS, MODE): the table's row with that id, if it has
+// the mode.  Rows without it are not instantiated; the others are, in table order (a left fold), all
+// from this one body -- the order their kernels take in the code object.
+template <bool STATS, int MODE, size_t... ROW>
+static hipError_t launch_rows(int v, const TraceParams& P, int cus, hipStream_t stream, std::index_sequence<ROW...>)
 {
-    switch (v) {
-    case 1: return launch_one<STATS, 0, 4, 0, 1, false, MODE>(P, stream);
-    case 4: return launch_one<STATS, 0, 4, 1, 5, false, MODE>(P, stream);
-    case 6: return launch_one<STATS, 1, 4, 1, 5, false, MODE>(P, stream);
-    case 20: return launch_one<STATS, 0, 4, 3, 5, false, MODE>(P, stream);
-    case 39: return launch_one<STATS, 1, 4, 224, 5, true, MODE>(P, stream);
-    case 40: return launch_one<STATS, 1, 4, kV40Walk, 5, true, MODE>(P, stream);
-    case 41: return launch_one<STATS, 0, 4, 14212, 5, true, MODE>(P, stream);
-    case 46: return launch_one<STATS, 0, 4, 14212, 4, true, MODE>(P, stream);
-    case 47: return launch_one<STATS, 1, 4, 224, 4, true, MODE>(P, stream);
-    case 48: return launch_one<STATS, 2, 4, 13216, 4, true, MODE>(P, stream);
-    // 60 / 61 instrumented: the six-wave builds themselves, so the counters of an
-    // instrumented launch (lane utilisation, repairs) come from the kernel that is timed
-    case 60: return launch_one<STATS, 1, 8, kV40Walk, 6, true, MODE>(P, stream);
-    case 61: return launch_one<STATS, 0, 4, 14212, 6, true, MODE>(P, stream);
-    case 90: return launch_one<false, 1, 4, 100000 + kV40Walk, 5, true, 0>(P, stream);   // test only: 40, no repair
-    case 91: return launch_one<false, 2, 4, 113216, 4, true, 0>(P, stream);              // A/B only: 48, no repair
+    hipError_t e = hipErrorInvalidValue;
+    (..., [&] {
+        constexpr Build B = kBuilds[ROW];
+        if constexpr ((B.modes & mode_bit(STATS, MODE)) != 0)
+            if (v == B.id) e = launch_one<STATS, B.SL, B.WPB, B.WW, B.MINW, B.PERSIST, MODE>(P, cus, stream);
+    }());
+    return e;
+}
+
+template <bool STATS, int MODE>
+static hipError_t launch_build(int v, const TraceParams& P, int cus, hipStream_t stream)
+{
+    return launch_rows<STATS, MODE>(v, P, cus, stream, std::make_index_sequence<kBuildCount>{});
+}
+
+// Strip-unit, run-ahead and adaptive launches (kModeStrip, kModeAhead, kModeAdaptive as a value): the
+// modes in which a lane that is done goes on with other work, built for the resumable walks (adaptive
+// launches also for the node-at-a-time fallbacks).
+static hipError_t launch_resumable(int v, int mode, const TraceParams& P, int cus, hipStream_t stream)
+{
+    switch (mode) {
+    case kModeStrip: return launch_build<false, kModeStrip>(v, P, cus, stream);
+    case kModeAhead: return launch_build<false, kModeAhead>(v, P, cus, stream);
+    case kModeAdaptive: return launch_build<false, kModeAdaptive>(v, P, cus, stream);
     default: return hipErrorInvalidValue;
     }
-}
-
-// Speculative-group launches (MODE 1) and their resume / pre-pass launches (MODE 2) exist for the
-// default variants only.
-template <int MODE>
-static hipError_t launch_grouped(int v, const TraceParams& P, hipStream_t stream)
-{
-    switch (v) {
-    case 39: return launch_one<false, 1, 4, 224, 5, true, MODE>(P, stream);
-    case 40: return launch_one<false, 1, 4, kV40Walk, 5, true, MODE>(P, stream);
-    case 41: return launch_one<false, 0, 4, 14212, 5, true, MODE>(P, stream);
-    case 46: return launch_one<false, 0, 4, 14212, 4, true, MODE>(P, stream);
-    case 60: return launch_one<false, 1, 8, kV40Walk, 6, true, MODE>(P, stream);
-    case 61: return launch_one<false, 0, 4, 14212, 6, true, MODE>(P, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-// Strip-unit launches (MODE 3) of the resumable persistent variants.
-static hipError_t launch_strip(int v, const TraceParams& P, hipStream_t stream)
-{
-    switch (v) {
-    case 40: return launch_one<false, 1, 4, kV40Walk, 5, true, 3>(P, stream);
-    case 41: return launch_one<false, 0, 4, 14212, 5, true, 3>(P, stream);
-    case 46: return launch_one<false, 0, 4, 14212, 4, true, 3>(P, stream);
-    case 60: return launch_one<false, 1, 8, kV40Walk, 6, true, 3>(P, stream);
-    case 61: return launch_one<false, 0, 4, 14212, 6, true, 3>(P, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-static bool strip_capable(int v) { return v == 40 || v == 41 || v == 46 || v == 60 || v == 61; }
-
-// Waves per SIMD a persistent variant is compiled for (its wave slots: CUs x 4 SIMDs x this).
-static uint32_t variant_waves(int v) { return v == 60 || v == 61 ? 6u : (v == 46 || v == 47 || v == 48 || v == 91) ? 4u : 5u; }
-
-// Run-ahead launches (MODE 4) of the resumable persistent variants.
-static hipError_t launch_ahead(int v, const TraceParams& P, hipStream_t stream)
-{
-    switch (v) {
-    case 40: return launch_one<false, 1, 4, kV40Walk, 5, true, 4>(P, stream);
-    case 41: return launch_one<false, 0, 4, 14212, 5, true, 4>(P, stream);
-    case 46: return launch_one<false, 0, 4, 14212, 4, true, 4>(P, stream);
-    case 60: return launch_one<false, 1, 8, kV40Walk, 6, true, 4>(P, stream);
-    case 61: return launch_one<false, 0, 4, 14212, 6, true, 4>(P, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-// Adaptive-sampling launches (MODE 5): every variant pick_variant returns by itself -- the resumable
-// persistent walks and the node-at-a-time fallbacks.
-static hipError_t launch_adaptive(int v, const TraceParams& P, hipStream_t stream)
-{
-    switch (v) {
-    case 4: return launch_one<false, 0, 4, 1, 5, false, 5>(P, stream);
-    case 6: return launch_one<false, 1, 4, 1, 5, false, 5>(P, stream);
-    case 40: return launch_one<false, 1, 4, kV40Walk, 5, true, 5>(P, stream);
-    case 41: return launch_one<false, 0, 4, 14212, 5, true, 5>(P, stream);
-    case 46: return launch_one<false, 0, 4, 14212, 4, true, 5>(P, stream);
-    case 60: return launch_one<false, 1, 8, kV40Walk, 6, true, 5>(P, stream);
-    case 61: return launch_one<false, 0, 4, 14212, 6, true, 5>(P, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-static bool adaptive_capable(int v) { return v == 4 || v == 6 || strip_capable(v); }
-
-// Tiles per dispatch unit.  A launch of few samples per pixel idles the lanes whose pixels finish
-// first for the rest of their tile; strips of K tiles let those lanes go on with the next tile.
-// Measured at 1080p (tools/call_loop.py, profiles/r04_call_loop.json): 1-spp progressive frames
-// 0.673 -> 0.646 ms (K = 2) -> 0.592 ms (K = 4); the reference's 8-spp calls 316 -> 320 ms (K = 2)
-// -> 466 ms (K = 4) per 128 calls -- units of several tiles are too few to balance the launch's tail
-// there.  Automatic: K = 4 for launches of at most 2 samples per pixel with at least ~6 tiles per
-// wave slot; the variant must be a strip-capable one.
-constexpr uint64_t kStripMaxSamples = 2;
-
-// `variant` is the one that runs (pick_variant's result, which already replaces a forced child-box
-// variant by a node-at-a-time one on scenes without the child-box layout or DFS leaf order).
-static uint32_t strip_tiles(const pt_context* ctx, int variant, uint32_t tiles, uint64_t samples)
-{
-    if (ctx->stripMode == 1 || !strip_capable(variant) || !ctx->cnodes) return 1;
-    if (ctx->stripMode >= 2) return (uint32_t)ctx->stripMode;
-    if (samples > kStripMaxSamples) return 1;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) return 1;
-    const uint64_t slots = (uint64_t)cus * 4 * 5;       // (the threshold was measured at five waves)
-    return (uint64_t)tiles >= 6 * slots ? 4u : 1u;
-}
-
-static bool variant_shipped(int v)
-{
-    return v == 0 || v == 1 || v == 4 || v == 6 || v == 20 || v == 40 || v == 41 || v == 46 || v == 47 || v == 48 || v == 39 ||
-           v == 60 || v == 61 || v == 91;   // 91: variant 48 without the rising-t_max rebuild (A/B of its cost only; not the reference's bits)
-}
-
-// Run-ahead (MODE 4): launches of kAheadMinSamples..kAheadMaxSamples samples per pixel make a stash
-// of the next call's first samples (the reference's render(cam, 8, ...) calls, main.cpp:272-279);
-// 1-2 spp progressive frames use strip units instead.
-constexpr uint64_t kAheadMinSamples = 3, kAheadMaxSamples = 64;
-// Cost pre-pass of a cold-start launch (render_impl): samples per pixel, and the smallest launch
-// (spp x chunks) that gets one.
-constexpr uint32_t kPrepassSpp = 2;
-constexpr uint64_t kPrepassMinSpp = 16;
-
-static int pick_variant(const pt_context* ctx)
-{
-    const size_t nodeBytes = 2 * (size_t)ctx->nodeCount * sizeof(float4);
-    if (ctx->variant > 0) {
-        // a child-box walk needs the child-box layout (leaf counts < 256) and leaves in DFS primitive
-        // order (repair_pending, ChildPair); without them the node-at-a-time walk runs, so grouped and
-        // strip launches (which exist only for the child-box walks) are never chosen for such scenes
-        const bool childBox = ctx->variant != 1 && ctx->variant != 4 && ctx->variant != 6;
-        return (childBox && (!ctx->dfsOrder || !ctx->cnodes)) ? (nodeBytes <= 48 * 1024 ? 6 : 4) : ctx->variant;
-    }
-    // measured on MI355X (tools/ab_variants.py, profiles/): child-box traversal (one dependent
-    // fetch per interior visit, leaves inline) with while-while leaf batching and 5 waves/SIMD
-    // wins on every scene; the child-box records are staged in LDS when they fit in 48 KB
-    // (cornell, the 484-object scene) and read through the caches otherwise (100k objects).
-    // Scenes outside the child-box encoding fall back to the node-at-a-time walk (launch_one).
-    // The resumable form wins everywhere (the wave shades its finished lanes once at most 12/64
-    // still walk), and so do persistent waves pulling tiles from a cursor (variants 30/34: +6% on
-    // the 484-object scene, +11% on 100k objects over the one-tile-per-wave grid, variants 28/26).
-    // A cache-read scene whose four LDS stacks per workgroup leave room for fewer than five
-    // workgroups per CU (BVH depth > 16) runs at 4 waves/SIMD anyway: variant 46 is variant 41
-    // compiled for that occupancy (128 VGPRs, no spill), +1% on the 100k-object scene (depth 19).
-    // Six waves per SIMD (variants 60 / 61: the same walks compiled for 80 VGPRs) when the LDS holds
-    // them: with the records in LDS as three 8-wave workgroups per CU (the records staged once per
-    // eight waves), with cache-read records as six 4-wave workgroups.  Measured on C3
-    // (profiles/r05_six_waves.json): 60 224.2 ms against 40 231.2; 61 237.5 against 41 245.7.
-    const size_t cbBytes = 4 * (size_t)ctx->cnodeCount * sizeof(float4);
-    const size_t waveBytes = (size_t)ctx->stackDepth * 64 * 8 + 64 * 12;   // a wave's stack + accumulation slice
-    const size_t ldsCap = 160 * 1024;
-    // (a BVH whose leaves are not in DFS primitive order cannot be descended by repair_pending: the
-    // node-at-a-time walks, which push every far child as the reference does)
-    if (!ctx->cnodes || !ctx->dfsOrder) return nodeBytes <= 48 * 1024 ? 6 : 4;
-    if (cbBytes <= 48 * 1024 && 3 * (cbBytes + 8 * waveBytes) <= ldsCap) return 60;
-    if (cbBytes <= 48 * 1024 && 5 * (cbBytes + 4 * waveBytes) <= ldsCap) return 40;
-    if (6 * 4 * waveBytes <= ldsCap) return 61;
-    return cbBytes <= 48 * 1024 ? 40 : (5 * 4 * waveBytes > ldsCap ? 46 : 41);
 }
 
 extern "C" {
@@ -974,6 +806,8 @@ PT_API int pt_create_banded(int device, uint32_t width, uint32_t height, uint32_
     ctx->rows = pt_band_rows(height, band_rows, band_offset, band_stride);
     auto bail = [&](int code) { pt_destroy(ctx); return code; };
     if (hipSetDevice(device) != hipSuccess) return bail(PT_ERR_HIP);
+    if (hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ctx->cus < 1)
+        return bail(PT_ERR_HIP);
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) return bail(PT_ERR_HIP);
     if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) return bail(PT_ERR_HIP);
     const size_t npix = (size_t)ctx->rows * width;
@@ -1198,7 +1032,7 @@ PT_API int pt_set_scene(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node
         ctx->cnodeCount = interior;
     }
     ctx->dfsOrder = dfsOrder;
-    ctx->orderStale = true;
+    ctx->orderState.stale = true;
     ctx->adMomValid = false;
     ctx->featValid = false;
     ++ctx->stateEpoch;
@@ -1259,7 +1093,7 @@ PT_API int pt_set_texture(pt_context* ctx, uint32_t handle, const float* rgba, u
     t.height = height;
     t.fwidth = (float)width;
     t.fheight = (float)height;
-    ctx->orderStale = true;
+    ctx->orderState.stale = true;
     ctx->adMomValid = false;
     ctx->featValid = false;
     ++ctx->stateEpoch;
@@ -1277,46 +1111,6 @@ PT_API int pt_set_skybox(pt_context* ctx, uint32_t handle)
     }
     ctx->skybox = handle;
     return PT_OK;
-}
-
-// Speculative sample groups: how many groups a launch uses (0 = a plain launch).  A launch of
-// `tiles` 8x8 tiles on a chip with `resident` wave slots is grouped when six work items per slot
-// would take at least 4 groups (under ~1.5 tiles per slot; with more, the cost-sorted list schedule
-// balances well enough), and then gets 3.5 items per slot, at least 4 groups, at most 8, each at
-// least 64 samples long.  Measured at six waves per SIMD (profiles/r05_six_waves.json, C3 rank-0
-// shares): N = 4 G = 4 / 5 / 6 / 8 78.4 / 79.5 / 80.6 / 83.7 ms; N = 8 G = 4 / 5 / 6 / 8 46.8 / 44.5 /
-// 44.5 / 46.0 ms (the six-items rule gave 5 and 8).
-static uint32_t ssg_groups(const pt_context* ctx, int variant, uint32_t tiles, uint32_t total)
-{
-    if (ctx->ssgMode == 1 || !(variant == 39 || strip_capable(variant))) return 0;
-    if (ctx->ssgMode >= 2) return std::min<uint32_t>((uint32_t)ctx->ssgMode, std::max(total, 1u));
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) return 0;
-    const uint64_t resident = (uint64_t)cus * 4 * variant_waves(variant);
-    // measured (tools/ssg_probe.py): with 2 or 3 groups the logging, the fold and the
-    // extra samples cost more than the shorter tail returns; from 4 groups on the tail wins
-    if ((6 * resident + tiles - 1) / tiles < 4) return 0;
-    uint64_t g = std::max<uint64_t>(4, (7 * resident + 2 * (uint64_t)tiles - 1) / (2 * (uint64_t)tiles));
-    g = std::min<uint64_t>({g, 8, total / 64});
-    return g >= 4 ? (uint32_t)g : 0;
-}
-
-// A plain launch with at most four tiles per SIMD runs every tile in one pass at four waves per
-// SIMD, so the fifth wave slot the default kernels are compiled for (96 VGPRs, with spills) buys
-// nothing: the same walk compiled for four waves (128 VGPRs, no spill) shortens every wave's chain,
-// and when the primitives fit in LDS next to the child-box records, four workgroups per CU still
-// fit and leaf tests read LDS instead of L1/L2.  Measured (tools/ab_variants.py, MI355X): cornell
-// 512x512x64 +5.5 % (48), one rank's share of 1080p x 1024 at N = 8 +4 % (47).
-static int small_grid_variant(const pt_context* ctx, int variant, uint32_t tiles)
-{
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) return variant;
-    if ((uint64_t)tiles > (uint64_t)cus * 4 * 4) return variant;
-    if (variant == 41 || variant == 61) return 46;
-    if (variant != 40 && variant != 60) return variant;
-    const size_t group = 4 * (size_t)ctx->cnodeCount * sizeof(float4) + 4 * (size_t)ctx->primCount * sizeof(float4) +
-                         4 * (size_t)ctx->stackDepth * 64 * 8 + 4 * 64 * 12;
-    return 4 * group <= 160 * 1024 ? 48 : 47;
 }
 
 // Grow-only device buffers of the speculative groups; false if the device is out of memory (the
@@ -1405,14 +1199,14 @@ static void ssg_release(pt_context* ctx)
 // in tile order.
 static int sort_order(pt_context* ctx, uint32_t tiles, uint64_t samples, uint32_t strip)
 {
-    ctx->orderSamples = samples;
-    ctx->orderStrip = strip;
+    ctx->orderState.samples = samples;
+    ctx->orderState.strip = strip;
     size_t bytes = ctx->sortTempBytes;
     PT_HIP_CHECK(ctx, rocprim::radix_sort_pairs_desc(ctx->sortTemp, bytes, ctx->tileCost, ctx->sortKeys, ctx->tileIds,
                                                      ctx->order, tiles, 0, 32, ctx->stream));
     PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->orderValid = true;
-    ctx->orderStale = false;
+    ctx->orderState.valid = true;
+    ctx->orderState.stale = false;
     return PT_OK;
 }
 
@@ -1444,7 +1238,7 @@ static int run_groups(pt_context* ctx, int variant, const TraceParams& P0, uint3
     PT_HIP_CHECK(ctx, hipGetLastError());
     P.ssgLook[0] = ctx->ssgLook[0];
     P.ssgLook[1] = ctx->ssgLook[1];
-    PT_HIP_CHECK(ctx, launch_grouped<1>(variant, P, s));
+    PT_HIP_CHECK(ctx, launch_build<false, kModeGrouped>(variant, P, ctx->cus, s));
     ssg_fold_kernel<<<pixBlocks, 256, 0, s>>>(P, 0, ctx->patchLog, ctx->patchEnd, ctx->patchCount, ssgCap, ctx->pairs,
                                               ctx->deadCount);
     PT_HIP_CHECK(ctx, hipGetLastError());
@@ -1466,7 +1260,7 @@ static int run_groups(pt_context* ctx, int variant, const TraceParams& P0, uint3
         if (dead == 0 || r > ctx->patchRounds) break;
         ctx->groupStats[1] = r;
         PT_HIP_CHECK(ctx, hipMemsetAsync(ctx->deadCount, 0, sizeof(uint32_t), s));
-        PT_HIP_CHECK(ctx, launch_grouped<1>(variant, Q, s));
+        PT_HIP_CHECK(ctx, launch_build<false, kModeGrouped>(variant, Q, ctx->cus, s));
         ssg_fold_kernel<<<pixBlocks, 256, 0, s>>>(P, r, ctx->patchLog, ctx->patchEnd, ctx->patchCount, ssgCap, ctx->pairs,
                                                   ctx->deadCount);
         PT_HIP_CHECK(ctx, hipGetLastError());
@@ -1476,28 +1270,9 @@ static int run_groups(pt_context* ctx, int variant, const TraceParams& P0, uint3
         R.ssgG = 0;
         R.numSlots = groupTiles;
         R.tileCost = nullptr;
-        PT_HIP_CHECK(ctx, launch_grouped<2>(variant, R, s));
+        PT_HIP_CHECK(ctx, launch_build<false, kModeAux>(variant, R, ctx->cus, s));
     }
     return PT_OK;
-}
-
-// Issue priority of a launch over `tiles` order positions (pt_set_issue_priority): position bounds of
-// priority levels 3, 2, 1; the rest run at 0.
-static void issue_priority(const pt_context* ctx, uint32_t tiles, uint32_t* prio)
-{
-    if (ctx->prioMode == 2) {
-        for (int i = 0; i < 3; ++i) prio[i] = ctx->prioBounds[i];
-        return;
-    }
-    for (int i = 0; i < 3; ++i) prio[i] = 0;
-    if (ctx->prioMode == 1) return;
-    // automatic: graded by quarter of the order -- the most expensive quarter of the tiles at
-    // priority 3, the next at 2, then 1, the cheapest quarter at 0.  Measured on the refined cost
-    // order (tools/sched_probe.py, profiles/r03_priority_policies.json): C3 N = 1 239.7 -> 235.8 ms,
-    // its N = 2 share 141.6 -> 128.6 ms, the C4 N = 8 share 552.6 -> 496.2 ms; no setting was slower.
-    prio[0] = tiles / 4;
-    prio[1] = tiles / 2;
-    prio[2] = tiles - tiles / 4;
 }
 
 // The launch parameters every trace launch of the context shares: buffers, scene, image, camera.
@@ -1541,144 +1316,118 @@ static void base_params(const pt_context* ctx, const pt_camera* cam, uint32_t sp
     for (int k = 0; k < 6; ++k) P.rootBox[k] = ctx->rootBox[k];
 }
 
-static int render_impl(pt_context* ctx, const pt_camera* cam, uint32_t spp, uint32_t chunks, int ignore, float* gpu_ms,
-                       pt_render_stats* stats)
+static SceneFacts scene_facts(const pt_context* ctx)
 {
-    if (!ctx || !cam) return PT_ERR_ARG;
-    if (gpu_ms) *gpu_ms = 0.0f;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (ctx->nodeCount < 1 || ctx->primCount < 1 || spp == 0 || chunks == 0 || ctx->rows == 0) return PT_OK;
-    // textures referenced by the launch must exist (the reference would read an invalid object)
-    if (ctx->skybox != 0 && ctx->hostTex[ctx->skybox - 1].texels == nullptr)
-        return fail(ctx, PT_ERR_STATE, "pt_render: skybox handle has no texture");
-    TraceParams P;
-    base_params(ctx, cam, spp, chunks, ignore, P);
-    ctx->adMomValid = false;              // the moments of an adaptive render no longer describe the buffer
-    // Tile scheduling: a pixel's samples are sequential (one XORWOW stream), so a tile is the
-    // smallest unit of work, and tiles differ several-fold in cost (sky vs geometry).  Every
-    // launch records each tile's cycle count; after a scene, texture or camera change the
-    // dispatch order is rebuilt on the device from the latest costs (most expensive first, a
-    // stable radix sort), so
-    // the launch tail consists of cheap tiles and the waves of a workgroup (which hold the
-    // group's LDS until the last one ends) have similar lengths.  A camera move keeps using the
-    // previous order for one launch.  The order changes which wave renders a tile, never how:
-    // results are identical.
-    const uint32_t tiles = P.tilesX * P.tilesY;
-    if (ctx->orderTiles != tiles) {
-        (void)hipFree(ctx->tileCost);
-        (void)hipFree(ctx->order);
-        (void)hipFree(ctx->tileIdle);
-        ctx->tileCost = nullptr;
-        ctx->order = nullptr;
-        ctx->tileIdle = nullptr;
-        ctx->orderTiles = 0;
-        ctx->orderValid = false;
-        PT_HIP_CHECK(ctx, hipMalloc(&ctx->tileCost, (size_t)tiles * sizeof(uint32_t)));
-        PT_HIP_CHECK(ctx, hipMalloc(&ctx->order, ((size_t)tiles + 64) * sizeof(uint32_t)));
-        (void)hipFree(ctx->sortKeys);
-        (void)hipFree(ctx->tileIds);
-        (void)hipFree(ctx->sortTemp);
-        ctx->sortKeys = ctx->tileIds = nullptr;
-        ctx->sortTemp = nullptr;
-        PT_HIP_CHECK(ctx, hipMalloc(&ctx->sortKeys, (size_t)tiles * sizeof(uint32_t)));
-        PT_HIP_CHECK(ctx, hipMalloc(&ctx->tileIds, (size_t)tiles * sizeof(uint32_t)));
-        ctx->sortTempBytes = 0;
-        PT_HIP_CHECK(ctx, rocprim::radix_sort_pairs_desc(nullptr, ctx->sortTempBytes, ctx->tileCost, ctx->sortKeys,
-                                                         ctx->tileIds, ctx->order, tiles, 0, 32, ctx->stream));
-        PT_HIP_CHECK(ctx, hipMalloc(&ctx->sortTemp, ctx->sortTempBytes ? ctx->sortTempBytes : 4));
-        PT_HIP_CHECK(ctx, hipMemsetAsync(ctx->tileCost, 0, (size_t)tiles * sizeof(uint32_t), ctx->stream));
-        // tiles as packed coordinates (tileY << 16 | tileX: the kernel needs no division by tilesX);
-        // slots past the last tile stay invalid (tileY = tilesY)
-        std::vector<uint32_t> ident((size_t)tiles + 64);
-        for (size_t i = 0; i < ident.size(); ++i)
-            ident[i] = i < tiles ? ((uint32_t)(i / P.tilesX) << 16) | (uint32_t)(i % P.tilesX) : P.tilesY << 16;
-        (void)hipFree(ctx->rowMajor);
-        ctx->rowMajor = nullptr;
-        PT_HIP_CHECK(ctx, hipMalloc(&ctx->rowMajor, ident.size() * sizeof(uint32_t)));
-        PT_HIP_CHECK(ctx, hipMemcpy(ctx->rowMajor, ident.data(), ident.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        PT_HIP_CHECK(ctx, hipMemcpy(ctx->order, ident.data(), ident.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        PT_HIP_CHECK(ctx, hipMemcpy(ctx->tileIds, ident.data(), (size_t)tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
-        ctx->orderTiles = tiles;
-        ctx->orderStale = true;
+    return {{ctx->nodeCount, ctx->cnodeCount, ctx->primCount, ctx->stackDepth}, ctx->cnodes != nullptr, ctx->dfsOrder};
+}
+
+// The cursor of the persistent builds.
+static int cursor_reserve(pt_context* ctx)
+{
+    if (ctx->tileCursor) return PT_OK;
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->tileCursor, 2 * sizeof(uint32_t)));
+    PT_HIP_CHECK(ctx, hipMemset(ctx->tileCursor, 0, 2 * sizeof(uint32_t)));
+    return PT_OK;
+}
+
+// Tile scheduling: a pixel's samples are sequential (one XORWOW stream), so a tile is the
+// smallest unit of work, and tiles differ several-fold in cost (sky vs geometry).  Every
+// launch records each tile's cycle count; after a scene, texture or camera change the
+// dispatch order is rebuilt on the device from the latest costs (most expensive first, a
+// stable radix sort), so
+// the launch tail consists of cheap tiles and the waves of a workgroup (which hold the
+// group's LDS until the last one ends) have similar lengths.  A camera move keeps using the
+// previous order for one launch.  The order changes which wave renders a tile, never how:
+// results are identical.
+// The buffers of that order for a frame of tilesX x tilesY tiles.
+static int order_reserve(pt_context* ctx, uint32_t tilesX, uint32_t tilesY)
+{
+    const uint32_t tiles = tilesX * tilesY;
+    if (ctx->orderTiles == tiles) return PT_OK;
+    (void)hipFree(ctx->tileCost);
+    (void)hipFree(ctx->order);
+    (void)hipFree(ctx->tileIdle);
+    ctx->tileCost = nullptr;
+    ctx->order = nullptr;
+    ctx->tileIdle = nullptr;
+    ctx->orderTiles = 0;
+    ctx->orderState.valid = false;
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->tileCost, (size_t)tiles * sizeof(uint32_t)));
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->order, ((size_t)tiles + 64) * sizeof(uint32_t)));
+    (void)hipFree(ctx->sortKeys);
+    (void)hipFree(ctx->tileIds);
+    (void)hipFree(ctx->sortTemp);
+    ctx->sortKeys = ctx->tileIds = nullptr;
+    ctx->sortTemp = nullptr;
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->sortKeys, (size_t)tiles * sizeof(uint32_t)));
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->tileIds, (size_t)tiles * sizeof(uint32_t)));
+    ctx->sortTempBytes = 0;
+    PT_HIP_CHECK(ctx, rocprim::radix_sort_pairs_desc(nullptr, ctx->sortTempBytes, ctx->tileCost, ctx->sortKeys,
+                                                     ctx->tileIds, ctx->order, tiles, 0, 32, ctx->stream));
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->sortTemp, ctx->sortTempBytes ? ctx->sortTempBytes : 4));
+    PT_HIP_CHECK(ctx, hipMemsetAsync(ctx->tileCost, 0, (size_t)tiles * sizeof(uint32_t), ctx->stream));
+    // tiles as packed coordinates (tileY << 16 | tileX: the kernel needs no division by tilesX);
+    // slots past the last tile stay invalid (tileY = tilesY)
+    std::vector<uint32_t> ident((size_t)tiles + 64);
+    for (size_t i = 0; i < ident.size(); ++i)
+        ident[i] = i < tiles ? ((uint32_t)(i / tilesX) << 16) | (uint32_t)(i % tilesX) : tilesY << 16;
+    (void)hipFree(ctx->rowMajor);
+    ctx->rowMajor = nullptr;
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->rowMajor, ident.size() * sizeof(uint32_t)));
+    PT_HIP_CHECK(ctx, hipMemcpy(ctx->rowMajor, ident.data(), ident.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    PT_HIP_CHECK(ctx, hipMemcpy(ctx->order, ident.data(), ident.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    PT_HIP_CHECK(ctx, hipMemcpy(ctx->tileIds, ident.data(), (size_t)tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+    ctx->orderTiles = tiles;
+    ctx->orderState.stale = true;
+    return PT_OK;
+}
+
+// The row-major order of strip units of K tiles (packed first tiles), kept for the last K.
+static int units_reserve(pt_context* ctx, uint32_t K, uint32_t tilesX, uint32_t tilesY)
+{
+    const uint32_t tiles = tilesX * tilesY, unitsX = (tilesX + K - 1) / K, units = unitsX * tilesY;
+    if (ctx->unitK == K && ctx->unitTiles == tiles) return PT_OK;
+    (void)hipFree(ctx->unitMajor);
+    ctx->unitMajor = nullptr;
+    std::vector<uint32_t> um((size_t)units + 64);
+    for (size_t i = 0; i < um.size(); ++i)
+        um[i] = i < units ? ((uint32_t)(i / unitsX) << 16) | (uint32_t)(i % unitsX * K) : tilesY << 16;
+    PT_HIP_CHECK(ctx, hipMalloc(&ctx->unitMajor, um.size() * sizeof(uint32_t)));
+    PT_HIP_CHECK(ctx, hipMemcpy(ctx->unitMajor, um.data(), um.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    ctx->unitK = K;
+    ctx->unitTiles = tiles;
+    return PT_OK;
+}
+
+static void set_priority(TraceParams& P, const PassPriority& pp)
+{
+    for (int i = 0; i < 3; ++i) P.prio[i] = pp.prio[i];
+    P.prioDealt = pp.dealt ? 1u : 0u;
+}
+
+// Execute a plan (pt_launch_plan.h): the buffers it needs, the cold-start pass, the main pass, the
+// order's rebuild.  P holds base_params.
+static int run_plan(pt_context* ctx, const pt_camera* cam, const LaunchInputs& in, LaunchPlan plan, TraceParams P,
+                    float* gpu_ms, pt_render_stats* stats)
+{
+    if (plan.dropOrder) {
+        ctx->orderState.valid = false;
+        ctx->orderState.stale = true;
     }
-    // Run-ahead across render() calls (MODE 4): a stash made by the previous launch is valid when
-    // this launch has its camera, scene, textures, sky and RNG state (stateEpoch); a context whose
-    // camera or state changed on the last two launches (a moving progressive camera) stops making
-    // stashes until it holds still again.
-    const bool sameKey = ctx->launched && memcmp(&ctx->lastCam, cam, sizeof(pt_camera)) == 0 &&
-                         ctx->lastState == ctx->stateEpoch;
-    ctx->aheadMisses = sameKey ? 0u : std::min(ctx->aheadMisses + 1u, 1000u);
-    const bool stashMatches = ctx->aheadValid && sameKey;
-    ctx->aheadValid = false;              // consumed or dropped; a making launch sets it again
-    ctx->launched = true;
-    ctx->lastState = ctx->stateEpoch;
-    if (memcmp(&ctx->lastCam, cam, sizeof(pt_camera)) != 0) {
-        ctx->orderStale = true;
-        ctx->lastCam = *cam;
-    }
-    const bool sorted = ctx->schedule == 0;
-    // Strip units (MODE 3, trace_kernel): launches of few samples per pixel dispatch row strips of K
-    // tiles, and a lane whose pixel is done moves on to the next tile of its strip.  The cost order
-    // is over units, so it is rebuilt when K changes.
-    const bool noRepair = !ctx->riseRepair;           // test knob: plain launches of variant 90 only
-    const uint64_t launchSamples = (uint64_t)spp * chunks;
-    // (strip units or sample groups forced by their knobs take precedence over automatic run-ahead)
-    const bool aheadCapable = !stats && !noRepair && ctx->cnodes && strip_capable(pick_variant(ctx)) && ctx->aheadMode != 1 &&
-                              (ctx->aheadMode == 2 || (ctx->stripMode < 2 && ctx->ssgMode < 2));
-    const bool aheadUse = aheadCapable && stashMatches && ctx->aheadMode != 3;   // 3: diagnostic, never consume
-    // Automatic run-ahead only where tiles wait for a wave slot: a grid that holds every tile in one
-    // pass (cornell 512x512: 4,096 tiles, 5,120-6,144 slots) has no next tile for a finished lane's
-    // wave to delay, and run-ahead measured neutral there (4.37-4.42 vs 4.35-4.36 ms)
-    // while it keeps the small-grid build from running.
-    bool aheadFits = true;
-    if (ctx->aheadMode == 0 && aheadCapable) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess)
-            aheadFits = (uint64_t)tiles > (uint64_t)cus * 4 * variant_waves(pick_variant(ctx));
-    }
-    const bool aheadMake = aheadCapable && (ctx->aheadMode == 2 ||
-        (launchSamples >= kAheadMinSamples && launchSamples <= kAheadMaxSamples && ctx->aheadMisses < 2 && aheadFits));
-    const bool ahead = aheadUse || aheadMake;
-    const uint32_t K = (sorted && !stats && !noRepair && !ahead) ? strip_tiles(ctx, pick_variant(ctx), tiles, launchSamples) : 1u;
-    const uint32_t unitsX = (P.tilesX + K - 1) / K, units = unitsX * P.tilesY;
-    if (K != ctx->orderStrip) {
-        ctx->orderValid = false;
-        ctx->orderStale = true;
-    }
-    if (K > 1 && (ctx->unitK != K || ctx->unitTiles != tiles)) {
-        (void)hipFree(ctx->unitMajor);
-        ctx->unitMajor = nullptr;
-        std::vector<uint32_t> um((size_t)units + 64);
-        for (size_t i = 0; i < um.size(); ++i)
-            um[i] = i < units ? ((uint32_t)(i / unitsX) << 16) | (uint32_t)(i % unitsX * K) : P.tilesY << 16;
-        PT_HIP_CHECK(ctx, hipMalloc(&ctx->unitMajor, um.size() * sizeof(uint32_t)));
-        PT_HIP_CHECK(ctx, hipMemcpy(ctx->unitMajor, um.data(), um.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        ctx->unitK = K;
-        ctx->unitTiles = tiles;
+    if (plan.refusal) return fail(ctx, PT_ERR_STATE, plan.refusal);
+    const uint32_t tiles = P.tilesX * P.tilesY, K = plan.K, total = P.spp * P.chunks, chunks = P.chunks;
+    const bool sorted = ctx->knobs.schedule == 0;
+    if (K > 1) {
+        const int rc = units_reserve(ctx, K, P.tilesX, P.tilesY);
+        if (rc != PT_OK) return rc;
     }
     uint32_t* const firstOrder = K > 1 ? ctx->unitMajor : ctx->rowMajor;
     P.strip = K;
-    P.order = (sorted && ctx->orderValid) ? ctx->order : firstOrder;
     P.tileCost = sorted ? ctx->tileCost : nullptr;
-    P.scatterWaves = ctx->schedule == 2 ? (uint32_t)(((size_t)ctx->rows * ctx->width + 63) / 64) : 0u;
-    if (P.scatterWaves) P.order = nullptr;          // scattered mapping: slot = wave index
-    if (!ctx->tileCursor) {
-        PT_HIP_CHECK(ctx, hipMalloc(&ctx->tileCursor, 2 * sizeof(uint32_t)));
-        PT_HIP_CHECK(ctx, hipMemset(ctx->tileCursor, 0, 2 * sizeof(uint32_t)));
-    }
+    P.scatterWaves = ctx->knobs.schedule == 2 ? (uint32_t)(((size_t)ctx->rows * ctx->width + 63) / 64) : 0u;
     P.tileCursor = ctx->tileCursor;
-    P.numSlots = units;
+    P.numSlots = plan.units;
     P.occCap = ctx->occupancy;
-    // Issue priority follows the order position, so it is meaningful only on a current cost order.
-    // A launch whose tile costs will rebuild the order (stale order, or this launch measures >= 4x
-    // the samples the order came from; see the rebuild below) runs without it: graded priority
-    // shortens the head quarter's tiles, and costs measured under it would rank those tiles lower
-    // on every rebuild (a feedback the order would carry over camera moves).
-    const bool rebuilds = ctx->schedule == 0 &&
-                          (ctx->orderStale || !ctx->orderValid || (uint64_t)spp * chunks >= 4 * ctx->orderSamples);
-    if (!rebuilds || ctx->prioMode == 2) issue_priority(ctx, units, P.prio);   // explicit bounds: always
-    P.prioDealt = ctx->prioMode == 0 && P.prio[0] != 0;
     if (ctx->traceTiles && stats && P.tileCost) {
         if (ctx->tileTrace && ctx->traceCap < tiles) {
             (void)hipFree(ctx->tileTrace);
@@ -1696,130 +1445,69 @@ static int render_impl(pt_context* ctx, const pt_camera* cam, uint32_t spp, uint
         PT_HIP_CHECK(ctx, hipMemsetAsync(ctx->tileIdle, 0, (size_t)tiles * sizeof(uint32_t), ctx->stream));
         P.tileIdle = ctx->tileIdle;
     }
-    int variant = pick_variant(ctx);
-    // speculative sample groups
-    const uint32_t total = spp * chunks;
-    // the fold state packs (sample in call, call) into one word as sIdx | c << 16 (ssg_fold_kernel)
-    const bool groupable = !stats && sorted && (uint64_t)spp * chunks < (1ull << 31) && spp <= 0xffffu && chunks <= 0xffffu;
-    uint32_t G = groupable && K == 1 && !noRepair && !ahead ? ssg_groups(ctx, variant, tiles, total) : 0;
-    if (!G && ctx->variant == 0 && K == 1 && !noRepair && !ahead) variant = small_grid_variant(ctx, variant, tiles);
-    // The sixth wave slot (variants 60 / 61) raises throughput but gives each wave a smaller share of
-    // the SIMD's issue: a plain launch of few tiles per slot, whose end is its heaviest tiles' sample
-    // chains, runs longer with it (the C4 N = 8 share, 2.6 tiles per six-wave slot: 532 against 498 ms;
-    // C3, 5.3 tiles per slot: 224.2 against 231.2; profiles/r05_six_waves.json).  Plain launches of
-    // fewer than 4 dispatch units per six-wave slot (also 1-spp strip-unit frames) run the five-wave build.
-    if (!G && ctx->variant == 0 && (variant == 60 || variant == 61)) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess ||
-            (uint64_t)units < 4ull * cus * 4 * 6)
-            variant = variant == 60 ? 40 : 41;
-    }
-    if (ahead) {
+    if (plan.aheadUse || plan.aheadMake) {
         if (!ctx->ahead) {
             const size_t n = std::max<size_t>((size_t)ctx->rows * ctx->width, 1);
             PT_HIP_CHECK(ctx, hipMalloc(&ctx->ahead, kAheadWords * n * sizeof(uint32_t)));
         }
         P.ahead = ctx->ahead;
-        P.aheadUse = aheadUse ? 1u : 0u;
-        P.aheadMake = aheadMake ? 1u : 0u;
+        P.aheadUse = plan.aheadUse ? 1u : 0u;
+        P.aheadMake = plan.aheadMake ? 1u : 0u;
     }
-    if (noRepair) {
-        if (variant == 60) variant = 40;              // (the no-repair build exists at five waves only)
-        if (variant != 40 || stats)
-            return fail(ctx, PT_ERR_STATE, "pt_set_rise_repair(0): only plain launches of variant 40 have a no-repair build");
-        variant = 90;
-    }
-    // (Round 3 sent grouped launches of at most one tile per wave slot to the undeferred walk, 39;
-    // measured again on the C3 N = 8 share it costs 8-10 %: 52.9 ms against 47.1 (40) and 47.8-48.9
-    // (60) with deferred shading, profiles/r05_six_waves.json.  Grouped launches keep the picked walk.)
     ctx->lastGroups = 0;
-    ctx->lastVariant = variant;
+    ctx->lastVariant = plan.build;
     memset(ctx->groupStats, 0, sizeof(ctx->groupStats));
     ++ctx->epoch;
-    uint32_t ssgCap = 0;
-    if (G) {
-        const uint32_t ssgN = total / G;
-        // an item runs its group and, where the next group's guess missed, into the group after it;
-        // further dead ends go to patch rounds
-        ssgCap = std::min<uint32_t>({total, 2 * ssgN + 64, 10000u});   // end offsets: 16-bit draw pairs (<= 6 per sample)
-        const size_t J = 2 * (size_t)G - 1;
-        if (!ssg_reserve(ctx, tiles, (size_t)tiles * J, (size_t)tiles * J * ssgCap, (size_t)tiles * ssgCap,
-                         (size_t)tiles * J * ssg_window_words(G, ssgN)))
-            G = 0;
+    if (plan.G) {
+        const size_t J = 2 * (size_t)plan.G - 1;
+        if (!ssg_reserve(ctx, tiles, (size_t)tiles * J, (size_t)tiles * J * plan.ssgCap, (size_t)tiles * plan.ssgCap,
+                         (size_t)tiles * J * ssg_window_words(plan.G, total / plan.G))) {
+            plan.G = plan.ssgCap = 0;             // out of memory: a plain launch of the planned build
+            plan_passes(in, plan);
+        }
     }
     // a plain launch after grouped ones releases the group logs (a stream synchronisation and frees
     // of up to ~15 GB): before the timed region starts
-    if (!G) ssg_release(ctx);
+    if (!plan.G) ssg_release(ctx);
     PT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    // Cold start (first launch, or the scene, a texture or the camera changed): no tile costs yet.
-    // Progressive 1-spp frames reuse the previous order for one launch.  A launch of several render()
-    // calls runs its FIRST call as a launch of its own in row-major order, sorts the tiles by that
-    // call's costs on the device and runs the other calls in that order -- nothing is computed twice,
-    // and two launches of 1 and chunks - 1 calls are the reference's calls exactly as one launch is
-    // (each call folds into the accumulation, ignoreHistory applies to the first).  Other launches
-    // (one call, or sample groups, which take their draw-pair guesses from it) run a short discarded
-    // pre-pass instead.  Either way the launch then runs with issue priority on that order
-    // (pt_set_cold_start; measured: one-shot C3 251-255 -> 238-240 ms, tools/cold_start.py); as its
-    // tile costs are measured under priority, the order rebuilt from them is biased toward the head's
-    // tiles, so the next launch rebuilds it again without priority (orderSamples = 0 below).
-    const bool cold = sorted && (ctx->orderStale || !ctx->orderValid) && (uint64_t)spp * chunks >= kPrepassMinSpp && !stats;
-    const bool splitCall = cold && chunks >= 2 && !G && K == 1 && !ahead && ctx->prepassSpp == 0;
-    bool biasedOrder = false;
-    if (splitCall) {
+    if (plan.cold != ColdStart::None) {
         TraceParams Q = P;
         Q.chunks = 1;
-        Q.order = firstOrder;
-        for (int i = 0; i < 3; ++i) Q.prio[i] = 0;        // row-major positions: no priority grading
-        Q.prioDealt = 0;
-        PT_HIP_CHECK(ctx, launch_variant<false>(variant, Q, ctx->stream));
-        const int rs = sort_order(ctx, tiles, spp, K);
-        if (rs != PT_OK) return rs;
-        P.order = ctx->order;
-        P.chunks = chunks - 1;
-        P.ignoreFirst = 0;                               // the first call is done
-        if (ctx->coldPriority && ctx->prioMode == 0) {
-            issue_priority(ctx, units, P.prio);
-            P.prioDealt = 1;
-            biasedOrder = true;
+        Q.order = firstOrder;                            // (a cold start is a sorted schedule's)
+        set_priority(Q, plan.coldPrio);
+        if (plan.cold == ColdStart::SplitCall) {
+            P.chunks = chunks - 1;
+            P.ignoreFirst = 0;                               // the first call is done
+        } else {
+            Q.spp = plan.coldSpp;
+            Q.ignoreFirst = 1;
+            Q.discard = 1;
+            Q.pairsOut = plan.coldPairs && ssg_reserve(ctx, tiles, 0, 0, 0) ? ctx->pairs : nullptr;
+            if (Q.pairsOut) ctx->pairsValid = true;
         }
-    } else if (cold) {
-        // pre-pass: kPrepassSpp samples per pixel from the pixels' current RNG state, nothing
-        // written back (discard)
-        TraceParams Q = P;
-        const bool guesses = G != 0;           // speculative groups also take their offset guesses from it
-        Q.spp = guesses ? 8u : (ctx->prepassSpp ? ctx->prepassSpp : kPrepassSpp);
-        Q.chunks = 1;
-        Q.ignoreFirst = 1;
-        Q.discard = 1;
-        Q.order = firstOrder;
-        for (int i = 0; i < 3; ++i) Q.prio[i] = 0;        // row-major positions: no priority grading
-        Q.prioDealt = 0;
-        Q.pairsOut = guesses && ssg_reserve(ctx, tiles, 0, 0, 0) ? ctx->pairs : nullptr;
-        if (Q.pairsOut) ctx->pairsValid = true;
-        PT_HIP_CHECK(ctx, Q.pairsOut ? launch_grouped<2>(variant, Q, ctx->stream)
-                                     : (K > 1 ? launch_strip(variant, Q, ctx->stream) : launch_variant<false>(variant, Q, ctx->stream)));
-        const int rs = sort_order(ctx, tiles, Q.spp, K);
+        PT_HIP_CHECK(ctx, Q.pairsOut ? launch_build<false, kModeAux>(plan.build, Q, ctx->cus, ctx->stream)
+                          : K > 1    ? launch_resumable(plan.build, kModeStrip, Q, ctx->cus, ctx->stream)
+                                     : launch_build<false, kModePlain>(plan.build, Q, ctx->cus, ctx->stream));
+        const int rs = sort_order(ctx, tiles, plan.coldSpp, K);
         if (rs != PT_OK) return rs;
-        P.order = ctx->order;
-        if (ctx->coldPriority && ctx->prioMode == 0) {
-            issue_priority(ctx, units, P.prio);
-            P.prioDealt = 1;
-            biasedOrder = true;
-        }
     }
-    if (G && P.tileCost) PT_HIP_CHECK(ctx, hipMemsetAsync(P.tileCost, 0, (size_t)tiles * sizeof(uint32_t), ctx->stream));
-    if (G) {
-        P.prioDealt = 0;           // (grouped positions are (tile, group) items: measured slower with it)
-        const int rc = run_groups(ctx, variant, P, G, tiles, ssgCap, ctx->stream);
+    P.order = P.scatterWaves ? nullptr : (plan.costOrder ? ctx->order : firstOrder);   // scattered mapping: slot = wave index
+    set_priority(P, plan.mainPrio);
+    if (plan.G) {
+        if (P.tileCost) PT_HIP_CHECK(ctx, hipMemsetAsync(P.tileCost, 0, (size_t)tiles * sizeof(uint32_t), ctx->stream));
+        const int rc = run_groups(ctx, plan.build, P, plan.G, tiles, plan.ssgCap, ctx->stream);
         if (rc != PT_OK) return rc;
-        ctx->lastGroups = G;
+        ctx->lastGroups = plan.G;
     } else {
-        PT_HIP_CHECK(ctx, stats ? launch_variant<true>(variant, P, ctx->stream)
-                                : ahead ? launch_ahead(variant, P, ctx->stream)
-                                : (K > 1 ? launch_strip(variant, P, ctx->stream) : launch_variant<false>(variant, P, ctx->stream)));
+        // (90 and 91 have no instrumented build: their counters read zero)
+        const bool counted = stats && build_has(plan.build, kInstrumented);
+        PT_HIP_CHECK(ctx, plan.mode == LaunchMode::Ahead   ? launch_resumable(plan.build, kModeAhead, P, ctx->cus, ctx->stream)
+                          : plan.mode == LaunchMode::Strip ? launch_resumable(plan.build, kModeStrip, P, ctx->cus, ctx->stream)
+                          : counted                        ? launch_build<true, kModePlain>(plan.build, P, ctx->cus, ctx->stream)
+                                                           : launch_build<false, kModePlain>(plan.build, P, ctx->cus, ctx->stream));
     }
     memcpy(ctx->lastLaunch, g_lastLaunch, sizeof(ctx->lastLaunch));
-    if (aheadMake) {
+    if (plan.aheadMake) {
         ctx->aheadValid = true;
         ctx->aheadCam = *cam;
         ctx->aheadState = ctx->stateEpoch;
@@ -1830,64 +1518,83 @@ static int render_impl(pt_context* ctx, const pt_camera* cam, uint32_t spp, uint
     float ms = 0.0f;
     PT_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     if (gpu_ms) *gpu_ms = ms;
-    // The order is rebuilt from this launch's tile costs when it is stale, or when this launch
-    // measured every tile over at least 4x as many samples as the costs the order came from (a cold
-    // start's 2-spp pre-pass, an 8-spp first launch): short launches rank tiles noisily, and a heavy
-    // tile ranked light is dispatched late and becomes the launch's tail.
-    if (sorted && (ctx->orderStale || !ctx->orderValid || total >= 4 * ctx->orderSamples)) {
+    if (plan.rebuildOrder) {
         const int rs = sort_order(ctx, tiles, total, K);
         if (rs != PT_OK) return rs;
-        if (biasedOrder) ctx->orderSamples = 0;          // costs measured under priority: rebuild once more
+        if (plan.biasedOrder) ctx->orderState.samples = 0;
     }
     if (stats) {
-        unsigned long long h[kStatWords];
-        PT_HIP_CHECK(ctx, hipMemcpy(h, ctx->stats, sizeof(h), hipMemcpyDeviceToHost));
-        stats->node_tests = h[0];
-        stats->prim_tests = h[1];
-        stats->hits = h[2];
-        stats->sky_lookups = h[3];
-        stats->segments = h[4];
-        stats->samples = h[5];
-        stats->wave_node_iters = h[6];
-        stats->wave_prim_iters = h[7];
-        stats->wave_hits = h[8];
-        stats->wave_sky = h[9];
-        stats->wave_segments = h[10];
-        stats->cycles_node_walk = h[11];
-        stats->cycles_leaf_tests = h[12];
-        stats->cycles_shading = h[13];
-        stats->cycles_total = h[14];
-        stats->cycles_lane_idle = h[15];
-        stats->leaf_rounds = h[16];
-        stats->family_execs = h[17];
-        stats->family_execs_compacted = h[18];
-        stats->leaf_round_lanes = h[19];
-        stats->leaf_pairs = h[20];
-        stats->family_execs_compacted_in_round = h[21];
-        stats->repairs = h[22];
+        static_assert(sizeof(pt_render_stats) == kStatWords * sizeof(uint64_t), "the counters in the order of pt_render_stats");
+        PT_HIP_CHECK(ctx, hipMemcpy(stats, ctx->stats, sizeof(*stats), hipMemcpyDeviceToHost));
     }
     return PT_OK;
+}
+
+// A render: validate, make sure the buffers exist, describe the launch, plan it, execute the plan.
+static int render_impl(pt_context* ctx, const pt_camera* cam, uint32_t spp, uint32_t chunks, int ignore, float* gpu_ms,
+                       pt_render_stats* stats)
+{
+    if (!ctx || !cam) return PT_ERR_ARG;
+    if (gpu_ms) *gpu_ms = 0.0f;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (ctx->nodeCount < 1 || ctx->primCount < 1 || spp == 0 || chunks == 0 || ctx->rows == 0) return PT_OK;
+    // textures referenced by the launch must exist (the reference would read an invalid object)
+    if (ctx->skybox != 0 && ctx->hostTex[ctx->skybox - 1].texels == nullptr)
+        return fail(ctx, PT_ERR_STATE, "pt_render: skybox handle has no texture");
+    TraceParams P;
+    base_params(ctx, cam, spp, chunks, ignore, P);
+    ctx->adMomValid = false;              // the moments of an adaptive render no longer describe the buffer
+    int rc = order_reserve(ctx, P.tilesX, P.tilesY);
+    if (rc == PT_OK) rc = cursor_reserve(ctx);
+    if (rc != PT_OK) return rc;
+    // A run-ahead stash made by the previous launch is valid when this launch has its camera, scene,
+    // textures, sky and RNG state (stateEpoch).
+    const bool sameCam = memcmp(&ctx->lastCam, cam, sizeof(pt_camera)) == 0;
+    const bool sameKey = ctx->launched && sameCam && ctx->lastState == ctx->stateEpoch;
+    ctx->aheadMisses = sameKey ? 0u : std::min(ctx->aheadMisses + 1u, 1000u);
+    const bool stashMatches = ctx->aheadValid && sameKey;
+    ctx->aheadValid = false;              // consumed or dropped; a making launch sets it again
+    ctx->launched = true;
+    ctx->lastState = ctx->stateEpoch;
+    if (!sameCam) {
+        ctx->orderState.stale = true;
+        ctx->lastCam = *cam;
+    }
+    LaunchInputs in = {};
+    in.cus = (uint32_t)ctx->cus;
+    in.tilesX = P.tilesX;
+    in.tilesY = P.tilesY;
+    in.spp = spp;
+    in.chunks = chunks;
+    in.instrumented = stats != nullptr;
+    in.scene = scene_facts(ctx);
+    in.knobs = ctx->knobs;
+    in.order = ctx->orderState;
+    in.stashMatches = stashMatches;
+    in.aheadMisses = ctx->aheadMisses;
+    return run_plan(ctx, cam, in, plan_launch(in), P, gpu_ms, stats);
 }
 
 PT_API int pt_set_cold_start(pt_context* ctx, uint32_t prepass_spp, int priority)
 {
     if (!ctx || prepass_spp > 64 || priority < 0 || priority > 1) return PT_ERR_ARG;
-    ctx->prepassSpp = prepass_spp;
-    ctx->coldPriority = priority != 0;
+    ctx->knobs.prepassSpp = prepass_spp;
+    ctx->knobs.coldPriority = priority != 0;
     return PT_OK;
 }
 
 PT_API int pt_set_run_ahead(pt_context* ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 3) return PT_ERR_ARG;
-    ctx->aheadMode = mode;
+    ctx->knobs.aheadMode = mode;
     return PT_OK;
 }
 
 PT_API int pt_set_rise_repair(pt_context* ctx, int enabled)
 {
     if (!ctx || enabled < 0 || enabled > 1) return PT_ERR_ARG;
-    ctx->riseRepair = enabled != 0;
+    ctx->knobs.riseRepair = enabled != 0;
     return PT_OK;
 }
 
@@ -1901,14 +1608,14 @@ PT_API int pt_set_zero_quadric_consts(pt_context* ctx, int type)
 PT_API int pt_set_strip_units(pt_context* ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 16) return PT_ERR_ARG;
-    ctx->stripMode = mode;
+    ctx->knobs.stripMode = mode;
     return PT_OK;
 }
 
 PT_API int pt_set_sample_groups(pt_context* ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 4096) return PT_ERR_ARG;
-    ctx->ssgMode = mode;
+    ctx->knobs.ssgMode = mode;
     return PT_OK;
 }
 
@@ -1976,10 +1683,10 @@ PT_API int pt_read_group_stats(const pt_context* ctx, uint32_t* dst)
 PT_API int pt_set_issue_priority(pt_context* ctx, int mode, uint32_t level3, uint32_t level2, uint32_t level1)
 {
     if (!ctx || mode < 0 || mode > 2 || (mode == 2 && !(level3 <= level2 && level2 <= level1))) return PT_ERR_ARG;
-    ctx->prioMode = mode;
-    ctx->prioBounds[0] = level3;
-    ctx->prioBounds[1] = level2;
-    ctx->prioBounds[2] = level1;
+    ctx->knobs.prioMode = mode;
+    ctx->knobs.prioBounds[0] = level3;
+    ctx->knobs.prioBounds[1] = level2;
+    ctx->knobs.prioBounds[2] = level1;
     return PT_OK;
 }
 
@@ -1993,8 +1700,8 @@ PT_API int pt_set_occupancy(pt_context* ctx, uint32_t workgroups_per_cu)
 PT_API int pt_set_schedule(pt_context* ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 2) return PT_ERR_ARG;
-    ctx->schedule = mode;
-    ctx->orderStale = true;
+    ctx->knobs.schedule = mode;
+    ctx->orderState.stale = true;
     return PT_OK;
 }
 
@@ -2071,17 +1778,15 @@ PT_API int pt_render_adaptive(pt_context* ctx, const pt_camera* camera, const pt
     if (!ap.reset && !ctx->adMomValid)
         return fail(ctx, PT_ERR_STATE, "pt_render_adaptive: reset = 0 needs the moments of an adaptive render; there has been "
                                        "none since the last plain render, RNG write or scene, texture or sky change");
-    const int variant = pick_variant(ctx);
-    if (!adaptive_capable(variant))
+    const int variant = picked_build(ctx->knobs.variant, scene_facts(ctx));
+    if (!build_has(variant, mode_bit(false, kModeAdaptive)))
         return fail(ctx, PT_ERR_ARG, "pt_render_adaptive: the kernel variant set has no adaptive build (0, 4, 6, 40, 41, 46, 60, 61 have)");
     if (ctx->rows == 0) return PT_OK;
     const uint32_t tilesX = (ctx->width + 7) / 8, tiles = tilesX * ((ctx->rows + 7) / 8);
     const int rr = adaptive_reserve(ctx, tiles);
     if (rr != PT_OK) return rr;
-    if (!ctx->tileCursor) {
-        PT_HIP_CHECK(ctx, hipMalloc(&ctx->tileCursor, 2 * sizeof(uint32_t)));
-        PT_HIP_CHECK(ctx, hipMemset(ctx->tileCursor, 0, 2 * sizeof(uint32_t)));
-    }
+    const int cr = cursor_reserve(ctx);
+    if (cr != PT_OK) return cr;
     TraceParams P;
     base_params(ctx, camera, ap.spp, 1, 0, P);
     P.tileCursor = ctx->tileCursor;
@@ -2108,7 +1813,7 @@ PT_API int pt_render_adaptive(pt_context* ctx, const pt_camera* camera, const pt
         P.numSlots = (count + 63) / 64;
         P.chunks = ap.min_calls;
         P.ignoreFirst = 1;
-        PT_HIP_CHECK(ctx, launch_adaptive(variant, P, ctx->stream));
+        PT_HIP_CHECK(ctx, launch_resumable(variant, kModeAdaptive, P, ctx->cus, ctx->stream));
         rounds = 1;
         ctx->adSteps = ap.min_calls;
         samples = (uint64_t)count * ap.min_calls * ap.spp;
@@ -2123,7 +1828,7 @@ PT_API int pt_render_adaptive(pt_context* ctx, const pt_camera* camera, const pt
         if (count == 0) break;            // nothing active: no launch
         P.adCount = count;
         P.numSlots = (count + 63) / 64;
-        PT_HIP_CHECK(ctx, launch_adaptive(variant, P, ctx->stream));
+        PT_HIP_CHECK(ctx, launch_resumable(variant, kModeAdaptive, P, ctx->cus, ctx->stream));
         ++rounds;
         ++ctx->adSteps;
         samples += (uint64_t)count * ap.spp;
@@ -2308,8 +2013,8 @@ PT_API int pt_read_tile_trace(pt_context* ctx, uint32_t* dst, uint32_t count)
 PT_API int pt_set_kernel_variant(pt_context* ctx, int variant)
 {
     if (!ctx) return PT_ERR_ARG;
-    if (!variant_shipped(variant)) return fail(ctx, PT_ERR_ARG, "pt_set_kernel_variant: not a shipped variant");
-    ctx->variant = variant;
+    if (variant != 0 && !build_settable(variant)) return fail(ctx, PT_ERR_ARG, "pt_set_kernel_variant: not a shipped variant");
+    ctx->knobs.variant = variant;
     return PT_OK;
 }
 

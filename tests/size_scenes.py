@@ -32,8 +32,8 @@ Tree:
     leaf, and with it its ancestors: the reference's walk, which pushes a far child whether or not
     the ray meets it, still fills its stack to R on every primary ray.
 
-Policy (expected_build()): a transcription BY HAND of the comments above pick_variant,
-small_grid_variant and launch_one and of DESIGN.md §4.1/§4.4 -- it never calls the library.  A policy
+Policy (expected_build()): a transcription BY HAND of the comments above picked_build and
+small_grid_build (csrc/pt_launch_plan.h) and launch_one and of DESIGN.md §4.1/§4.4 -- it never calls the library.  A policy
 change must edit it knowingly.
 """
 from __future__ import annotations
@@ -257,8 +257,8 @@ def oracle_scene(sc: SizeScene, path: pathlib.Path, W: int, H: int):
 # ------------------------------------------------------------------------------------------------
 # the documented policy, by hand
 # ------------------------------------------------------------------------------------------------
-LDS_CAP = 160 * 1024          # bytes of LDS a workgroup may use (launch_one: "lds > 160 * 1024")
-KB48 = 48 * 1024              # "staged in LDS when they fit in 48 KB" (pick_variant)
+LDS_CAP = 160 * 1024          # bytes of LDS a workgroup may use (launch_one: "lds > kLdsLimit")
+KB48 = 48 * 1024              # "staged in LDS when they fit in 48 KB" (picked_build)
 
 # build -> (what is staged: 0 nothing, 1 records / nodes, 2 records and primitives;
 #           waves per workgroup; walks child-box records)
