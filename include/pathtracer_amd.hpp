@@ -211,7 +211,10 @@ public:
     };
     AdaptiveResult renderAdaptive(const Camera& camera, uint32_t spp, uint32_t minCalls, uint32_t maxCalls, float tolerance,
                                   float floor = 0.01f, bool reset = true);
-    bool adaptive() const { return m_adaptive; }     // the buffer holds an adaptive render
+    // The buffer holds an adaptive render: from renderAdaptive until the next launch that writes the
+    // accumulation, through this class or through the device layer (pt_holds_adaptive).  A scene, texture or
+    // sky change does not end it: the image calls go on dividing every pixel by its own number of calls.
+    bool adaptive() const;
     // First-hit feature buffers and the edge-avoiding a-trous denoiser (pt_render_features, pt_denoise,
     // pt_hip.h).  renderFeatures traces each pixel's first-sample ray and keeps three float4 planes (albedo +
     // primitive, normal + distance, position + flags); featurePlane returns one (borrowed, rows x width x 4).

@@ -227,7 +227,17 @@ typedef struct pt_adaptive_result {
 
 PT_API int pt_render_adaptive(pt_context *ctx, const pt_camera *camera, const pt_adaptive_params *params,
                               pt_adaptive_result *result);
-/* Moments of the last adaptive render: rows x width x 3 (m1, m2, n -- n as uint32 bits). */
+/* The context keeps two facts about an adaptive render apart:
+ *   "the counts describe the buffer": every pixel's accumulation value is the sum of its own n calls.  True
+ *   from the end of a pt_render_adaptive until the next launch that writes the accumulation (a pt_render that
+ *   launches, or the next pt_render_adaptive).  A scene, texture, sky or RNG-state change writes neither the
+ *   accumulation nor the counts, so the three reads below and pt_denoise go on returning the same image.
+ *   "the moments can be continued": the former, and no scene, texture, sky or RNG-state change since -- what
+ *   reset = 0 needs (samples of another scene or stream must not be folded into the same moments).
+ * pt_holds_adaptive: 1 while the counts describe the buffer, else 0. */
+PT_API int pt_holds_adaptive(const pt_context *ctx);
+/* Moments of the last adaptive render: rows x width x 3 (m1, m2, n -- n as uint32 bits).  This and the two
+ * reads below: PT_ERR_STATE unless the counts describe the buffer. */
 PT_API int pt_read_moments(pt_context *ctx, float *dst);
 /* accum / (float)n per pixel (rows x width float4): getHDRImageData's units with frames = calls. */
 PT_API int pt_read_adaptive_hdr(pt_context *ctx, float *dst);
@@ -451,10 +461,10 @@ typedef struct pt_denoise_params {
 } pt_denoise_params;
 
 /* Filters the context's image: C = accumulation * (1 / max(frames, 1)), the HDR read-out's arithmetic, or,
- * when the buffer holds an adaptive render, accumulation / n per pixel (pt_read_adaptive_hdr's; `frames`
- * is not used then); features = the planes of the last pt_render_features.  The accumulation is not
- * changed.  PT_ERR_STATE, naming the reason, when there are no feature planes or the scene or a texture
- * changed since; PT_ERR_ARG, naming the reason, on a context that does not hold the whole frame (the
+ * while the counts of an adaptive render describe the buffer (pt_holds_adaptive), accumulation / n per pixel
+ * (pt_read_adaptive_hdr's; `frames` is not used then); features = the planes of the last
+ * pt_render_features.  The accumulation is not changed.  PT_ERR_STATE, naming the reason, when there are
+ * no feature planes or the scene or a texture changed since; PT_ERR_ARG, naming the reason, on a context that does not hold the whole frame (the
  * filter needs every pixel's neighbours: gather the frame and use pt_denoise_image). */
 PT_API int pt_denoise(pt_context *ctx, uint32_t frames, const pt_denoise_params *params);
 /* hipEvent times in ms of the last pt_denoise's kernels, 10 floats: prepare, iterations 0..7 (0 for

@@ -327,7 +327,9 @@ class Pathtracer:
 
     @property
     def adaptive(self) -> bool:
-        """The buffer holds an adaptive render (pixels with different numbers of calls)."""
+        """The buffer holds an adaptive render (pixels with different numbers of calls): until the next render
+        writes it.  While it is true, moments() and the image calls succeed, whatever scene, texture or RNG
+        state was set since."""
         return bool(N.host().pth_renderer_adaptive(self._r))
 
     def moments(self) -> np.ndarray:
@@ -393,8 +395,9 @@ class Pathtracer:
             planes = getattr(self, "_planes", None)
             if planes is None:
                 raise PathtracerError(N.PT_ERR_STATE, "denoise: no feature planes (call features(camera) first)")
-            if self.adaptive:
-                color = self.get_hdr_image_data()
+            if N.hip().pt_holds_adaptive(self._ctx):
+                # the image pt_denoise filters (pt_read_adaptive_hdr's arithmetic), never an earlier denoised one
+                color = self.accum() / np.maximum(self.sample_counts(), 1).astype(np.float32)[..., None]
             else:
                 color = self.accum() * (np.float32(1.0) / np.float32(max(f, 1)))
             params.sigma_color = auto_sigma_color(color, *planes, demodulate=demod)

@@ -88,6 +88,7 @@ _HIP_SYMBOLS = {
     "pt_render_instrumented": (C.c_int, [C.c_void_p, P(PtCamera), C.c_uint32, C.c_uint32, C.c_int, P(C.c_float),
                                          P(PtRenderStats)]),
     "pt_render_adaptive": (C.c_int, [C.c_void_p, P(PtCamera), P(PtAdaptiveParams), P(PtAdaptiveResult)]),
+    "pt_holds_adaptive": (C.c_int, [C.c_void_p]),
     "pt_read_moments": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "pt_read_adaptive_hdr": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "pt_tonemap_adaptive": (C.c_int, [C.c_void_p, P(C.c_uint8)]),

@@ -111,26 +111,32 @@ void Pathtracer::renderChunks(const Camera& camera, uint32_t spp, uint32_t chunk
 {
     // after renderAdaptive the pixels hold different numbers of calls: one frame counter cannot
     // normalise a buffer that goes on accumulating (ignoreHistory starts a uniform buffer again)
-    if (m_adaptive && !ignoreHistory)
+    if (adaptive() && !ignoreHistory)
         check(PT_ERR_STATE, "render: the buffer holds an adaptive render; continue it with renderAdaptive(reset = false) "
                             "or start over with ignoreHistory");
-    m_adaptive = false;
-    m_denoised = false;
-    if (ignoreHistory) m_accumulatedFrames = 0;
     m_timing = 0.0f;
     const pt_camera cam = camera.toDevice();
     float ms = 0.0f;
     if (m_group) check(pt_group_render(m_group, &cam, spp, chunks, ignoreHistory ? 1 : 0, &ms), "pt_group_render");
     else check(pt_render(m_ctx, &cam, spp, chunks, ignoreHistory ? 1 : 0, &ms), "pt_render");
+    // the flags move once the call has succeeded: a refused render changes nothing, and one that launched
+    // nothing (spp or chunks 0) leaves an adaptive buffer adaptive
+    m_adaptive = adaptive();
+    m_denoised = false;
+    if (ignoreHistory) m_accumulatedFrames = 0;
     m_timing = ms;
     m_accumulatedFrames += chunks;
 }
+
+// m_adaptive says that this class made an adaptive render; the device context says whether its per-pixel
+// counts still describe the buffer (a pt_render on the context, past this class, ends that too)
+bool Pathtracer::adaptive() const { return m_adaptive && !m_group && pt_holds_adaptive(m_ctx) != 0; }
 
 Pathtracer::AdaptiveResult Pathtracer::renderAdaptive(const Camera& camera, uint32_t spp, uint32_t minCalls, uint32_t maxCalls,
                                                       float tolerance, float floor, bool reset)
 {
     if (m_group) check(PT_ERR_STATE, "renderAdaptive: not available on a device group");
-    if (!reset && !m_adaptive) check(PT_ERR_STATE, "renderAdaptive: reset = false needs a previous adaptive render");
+    if (!reset && !adaptive()) check(PT_ERR_STATE, "renderAdaptive: reset = false needs a previous adaptive render");
     m_timing = 0.0f;
     const pt_camera cam = camera.toDevice();
     const pt_adaptive_params ap = {spp, minCalls, maxCalls, tolerance, floor, reset ? 1 : 0};
@@ -165,8 +171,16 @@ float Pathtracer::denoise(const DenoiseOptions& o)
     if (!(o.sigmaColor > 0.0f)) {
         // automatic: a factor times the median luminance of the kept pixels' (demodulated) colour
         const size_t npix = (size_t)localRows() * m_width;
+        const bool was = m_denoised;   // the statistic is of the image to be filtered; a refusal below changes nothing
         m_denoised = false;
-        const float* c = getHDRImageData();
+        const float* c = nullptr;
+        try {
+            c = getHDRImageData();
+        } catch (...) {
+            m_denoised = was;
+            throw;
+        }
+        m_denoised = was;
         std::vector<float> a(npix * 4), n(npix * 4), q(npix * 4), lum;
         check(pt_read_features(m_ctx, 0, a.data()), "pt_read_features");
         check(pt_read_features(m_ctx, 1, n.data()), "pt_read_features");
@@ -225,7 +239,7 @@ float* Pathtracer::getHDRImageData()
         check(pt_read_denoised(m_ctx, m_cpuAccumBuffer.data()), "pt_read_denoised");
         return m_cpuAccumBuffer.data();
     }
-    if (m_adaptive) {                 // every pixel over its own number of calls
+    if (adaptive()) {                 // every pixel over its own number of calls
         check(pt_read_adaptive_hdr(m_ctx, m_cpuAccumBuffer.data()), "pt_read_adaptive_hdr");
         return m_cpuAccumBuffer.data();
     }
@@ -246,7 +260,7 @@ char* Pathtracer::getImageData()
         check(pt_tonemap_denoised(m_ctx, (uint8_t*)m_cpuResultBuffer.data()), "pt_tonemap_denoised");
         return m_cpuResultBuffer.data();
     }
-    if (m_adaptive) {
+    if (adaptive()) {
         check(pt_tonemap_adaptive(m_ctx, (uint8_t*)m_cpuResultBuffer.data()), "pt_tonemap_adaptive");
         return m_cpuResultBuffer.data();
     }

@@ -166,7 +166,7 @@ PT_API int pt_denoise(pt_context* ctx, uint32_t frames, const pt_denoise_params*
     float4* color = ctx->dnBuf;
     const float inv = 1.0f / fmaxf((float)frames, 1.0f);
     dn_color_kernel<<<(unsigned)((npix + 255) / 256), 256, 0, ctx->stream>>>(
-        color, ctx->accum, ctx->adMomValid ? ctx->adMom + 2 * npix : nullptr, npix, inv);
+        color, ctx->accum, ctx->adCountsValid ? ctx->adMom + 2 * npix : nullptr, npix, inv);
     PT_HIP_CHECK(ctx, hipGetLastError());
     PT_HIP_CHECK(ctx, denoise_run(ctx->stream, *params, ctx->width, ctx->height, color, ctx->feat, ctx->dnBuf + npix,
                                   ctx->dnBuf + 2 * npix, ctx->dnBuf + 3 * npix, ctx->dnBuf + 4 * npix,

@@ -552,7 +552,8 @@ struct pt_context {
     uint32_t groupStats[10] = {}; // G, patch rounds, dead-end pixels after fold rounds 0..7
     // adaptive sampling (pt_render_adaptive): per-pixel moments and the compaction buffers
     uint32_t* adMom = nullptr;        // [3][pixels]: m1, m2 (float bits), n
-    bool adMomValid = false;          // the moments describe the accumulation buffer
+    bool adMomValid = false;          // the moments can be continued (reset = 0): scene, textures, sky and RNG are theirs
+    bool adCountsValid = false;       // the per-pixel counts describe the accumulation buffer (the adaptive reads)
     uint32_t adSteps = 0;             // steps (calls of the active pixels) made since the last reset
     uint8_t* adFlag = nullptr;        // [pixels] has its minimum of calls and is not converged
     unsigned long long* adMasks = nullptr;   // [tiles] ballot of the tile's active pixels
@@ -1544,7 +1545,8 @@ static int render_impl(pt_context* ctx, const pt_camera* cam, uint32_t spp, uint
         return fail(ctx, PT_ERR_STATE, "pt_render: skybox handle has no texture");
     TraceParams P;
     base_params(ctx, cam, spp, chunks, ignore, P);
-    ctx->adMomValid = false;              // the moments of an adaptive render no longer describe the buffer
+    ctx->adMomValid = false;              // the moments and counts of an adaptive render no longer describe the buffer
+    ctx->adCountsValid = false;
     int rc = order_reserve(ctx, P.tilesX, P.tilesY);
     if (rc == PT_OK) rc = cursor_reserve(ctx);
     if (rc != PT_OK) return rc;
@@ -1799,6 +1801,7 @@ PT_API int pt_render_adaptive(pt_context* ctx, const pt_camera* camera, const pt
     ++ctx->stateEpoch;
     ++ctx->epoch;
     ctx->adMomValid = false;              // until the render is complete
+    ctx->adCountsValid = false;
     ctx->lastGroups = 0;
     ctx->lastVariant = variant;
     PT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -1839,6 +1842,7 @@ PT_API int pt_render_adaptive(pt_context* ctx, const pt_camera* camera, const pt
     float ms = 0.0f;
     PT_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     ctx->adMomValid = true;
+    ctx->adCountsValid = true;
     if (result) {
         result->rounds = rounds;
         result->samples = samples;
@@ -1847,10 +1851,12 @@ PT_API int pt_render_adaptive(pt_context* ctx, const pt_camera* camera, const pt
     return PT_OK;
 }
 
+PT_API int pt_holds_adaptive(const pt_context* ctx) { return ctx && ctx->adCountsValid ? 1 : 0; }
+
 PT_API int pt_read_moments(pt_context* ctx, float* dst)
 {
     if (!ctx || !dst) return PT_ERR_ARG;
-    if (!ctx->adMomValid) return fail(ctx, PT_ERR_STATE, "pt_read_moments: no adaptive render describes the buffer");
+    if (!ctx->adCountsValid) return fail(ctx, PT_ERR_STATE, "pt_read_moments: no adaptive render describes the buffer");
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     const size_t npix = (size_t)ctx->rows * ctx->width;
@@ -1864,7 +1870,7 @@ PT_API int pt_read_moments(pt_context* ctx, float* dst)
 PT_API int pt_read_adaptive_hdr(pt_context* ctx, float* dst)
 {
     if (!ctx || !dst) return PT_ERR_ARG;
-    if (!ctx->adMomValid) return fail(ctx, PT_ERR_STATE, "pt_read_adaptive_hdr: no adaptive render describes the buffer");
+    if (!ctx->adCountsValid) return fail(ctx, PT_ERR_STATE, "pt_read_adaptive_hdr: no adaptive render describes the buffer");
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     const size_t npix = (size_t)ctx->rows * ctx->width;
@@ -1881,7 +1887,7 @@ PT_API int pt_read_adaptive_hdr(pt_context* ctx, float* dst)
 PT_API int pt_tonemap_adaptive(pt_context* ctx, uint8_t* dst)
 {
     if (!ctx || !dst) return PT_ERR_ARG;
-    if (!ctx->adMomValid) return fail(ctx, PT_ERR_STATE, "pt_tonemap_adaptive: no adaptive render describes the buffer");
+    if (!ctx->adCountsValid) return fail(ctx, PT_ERR_STATE, "pt_tonemap_adaptive: no adaptive render describes the buffer");
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->rows * ctx->width;
     if (npix == 0) return PT_OK;

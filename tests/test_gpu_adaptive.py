@@ -105,6 +105,30 @@ def test_continuation(gpu_available, scenes):
     assert e.value.code == N.PT_ERR_STATE
 
 
+def test_image_reads_survive_a_scene_or_rng_change(gpu_available, scenes):
+    # neither call writes the accumulation or the counts: the image stays readable and the same; only the
+    # continuation (reset = False) is refused, as pt_hip.h documents
+    pt, cam = tracer(scenes, "cornell")
+    pt.render_adaptive(cam, **PARAMS)
+    hdr, ldr, m = pt.get_hdr_image_data(), pt.get_image_data(), pt.moments()
+    for change in (lambda: pt.set_rng_state(pt.rng_state()), lambda: pt.load_scene(str(scenes / "test_shapes.scene.json"))):
+        change()
+        assert pt.adaptive and np.array_equal(bits(pt.moments()), bits(m))
+        assert np.array_equal(bits(pt.get_hdr_image_data()), bits(hdr)) and np.array_equal(pt.get_image_data(), ldr)
+        with pytest.raises(pa.PathtracerError) as e:
+            pt.render_adaptive(cam, **dict(PARAMS, reset=False))
+        assert e.value.code == N.PT_ERR_STATE
+
+
+def test_a_device_layer_render_ends_the_adaptive_state(gpu_available, scenes):
+    # pt_render past the host layer: the counts no longer describe the buffer, and the flag follows
+    pt, cam = tracer(scenes, "cornell")
+    pt.render_adaptive(cam, **PARAMS)
+    pt.render_raw(cam, PARAMS["spp"], 1, False)
+    assert not pt.adaptive and pt.frames == 0
+    assert np.array_equal(bits(pt.get_hdr_image_data()), bits(pt.accum())) and pt.get_image_data().shape == (44, 60, 4)
+
+
 def test_bad_arguments(gpu_available, scenes):
     pt, cam = tracer(scenes, "cornell")
     for bad in (dict(spp=0), dict(min_calls=1), dict(max_calls=1), dict(tolerance=-1.0), dict(floor=-0.5),

@@ -168,6 +168,40 @@ def test_after_an_adaptive_render_every_pixel_is_over_its_own_count(gpu_availabl
     assert np.array_equal(pt.sample_counts(), n)
 
 
+def test_after_an_adaptive_render_and_a_scene_load_the_counts_still_divide(gpu_available, scenes):
+    # the scene load voids the planes and the continuation, not the counts: the filter's input is the image the reads return
+    pt = pa.Pathtracer(60, 44)
+    cam = pt.load_scene(str(scenes / "cornell_box.scene.json"))
+    pt.render_adaptive(cam, spp=4, min_calls=2, max_calls=8, tolerance=0.2)
+    hdr = pt.accum() / pt.sample_counts().astype(np.float32)[..., None]
+    cam = pt.load_scene(str(scenes / "cornell_box.scene.json"))
+    feats = pt.features(cam)
+    out = pt.denoise(**PARAMS)
+    want = dm.model(hdr, *feats["planes"], *MODEL_ARGS)
+    assert dm.same_words(out, want), first_difference(out, want)
+    assert dm.same_words(pt.get_hdr_image_data(), hdr)
+
+
+def test_the_automatic_sigma_is_of_the_undenoised_image_and_a_refusal_changes_nothing(gpu_available, scenes):
+    pt = pa.Pathtracer(60, 44)
+    cam = pt.load_scene(str(scenes / "cornell_box.scene.json"))
+    pt.render_adaptive(cam, spp=4, min_calls=2, max_calls=8, tolerance=0.2)
+    hdr, feats = pt.get_hdr_image_data(), pt.features(cam)
+    params, host = pa.denoise_params(iterations=3, sigma_color=0.4), N.host()
+    N.check_host(host.pth_renderer_denoise(pt._r, N.C.byref(params), 0, None))       # the image calls return the denoised image now
+    denoised = pt.get_hdr_image_data()
+    assert not dm.same_words(denoised, hdr)
+    d = pa.DENOISE_DEFAULTS
+    sigma = pa.auto_sigma_color(hdr, *feats["planes"], demodulate=d["demodulate"])
+    want = dm.model(hdr, *feats["planes"], d["iterations"], sigma, d["sigma_plane"], d["normal_power_log2"], 1)
+    assert dm.same_words(pt.denoise(), want)
+    # a refused host-layer denoise (the planes are void) leaves the image calls where they were
+    tex = np.ones((4, 4, 4), dtype=np.float32)
+    N.check_ctx(N.hip().pt_set_texture(pt._ctx, 1, tex.ctypes.data_as(N.C.POINTER(N.C.c_float)), 4, 4), pt._ctx)
+    assert host.pth_renderer_denoise(pt._r, N.C.byref(params), 1, None) == N.PT_ERR_STATE
+    assert host.pth_renderer_denoised(pt._r) == 1 and dm.same_words(pt.get_hdr_image_data(), want)
+
+
 def test_host_layer_and_cli(gpu_available, scenes, tmp_path):
     import subprocess
     from PIL import Image

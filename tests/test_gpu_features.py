@@ -17,6 +17,7 @@ import pytest
 
 import pathtracercuda_amd as pa
 import size_scenes as ss
+from first_hit import first_hits, twin  # noqa: F401  (test_gpu_features_geometry imports them from here)
 from oracle import pyoracle as po
 from pathtracercuda_amd import _native as N
 from test_gpu_parity import _set_caller_bvh
@@ -58,26 +59,6 @@ def albedo_table(osc):
         else:
             out[i] = list(m.baseColor)
     return out
-
-
-def twin(osc, emission):
-    """The scene with every material LAMBERT, base colour 0, no texture, emission[i]; no sky."""
-    t = po.OracleScene()
-    t.camera, t.nodes, t.node_count, t.prim_count = osc.camera, osc.nodes, osc.node_count, osc.prim_count
-    prims = (po.Hittable * osc.prim_count).from_buffer_copy(bytes(osc.prims)[:osc.prim_count * C.sizeof(po.Hittable)])
-    for i in range(osc.prim_count):
-        m = prims[i].mat
-        m.baseColor[:] = [0.0, 0.0, 0.0]
-        m.emissive[:] = [float(v) for v in emission[i]]
-        m.textureIndex, m.materialType = 0, 0
-    t.prims = prims
-    return t
-
-
-def first_hits(osc, emission, W, H, tiling):
-    ref = po.OracleRenderer(twin(osc, emission), W, H, tiling[1], tiling[2], band_rows=tiling[0])
-    ref.render(osc.camera, 1, True)
-    return ref.accum
 
 
 CASES = {
