@@ -6,6 +6,7 @@
 #   pathtracercuda_amd/lib/host_sanitize_check  ASan/UBSan mutation check of the host parsers (CPU)
 #   pathtracercuda_amd/lib/leaf_forms_check  exact vs fast form of the cube leaf test (CPU; `make leafcheck` runs it)
 #   pathtracercuda_amd/lib/launch_plan_check  the launch policy and the build table on the host, for tests/test_launch_plan.py (CPU)
+#   pathtracercuda_amd/lib/ctx_state_check  what a context carries between calls on the host, for tests/test_ctx_state.py (CPU)
 #   oracle/liboracle.so                   CPU restatement (test infrastructure only)
 #   oracle/_ref/libptref.so               the reference's own source built for the host, when a checkout
 #                                         of it is at $(REF) (test infrastructure only; oracle/Makefile)
@@ -31,7 +32,7 @@ HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fno-slp-vec
 CXXFLAGS ?= -O2 -std=c++17 -ffp-contract=off -fno-fast-math -fPIC -Iinclude -I$(SRC)/host -Wall -Wextra \
             -Wno-unused-parameter -Wno-missing-field-initializers
 
-all: $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer $(LIB)/fp_exhaustive $(LIB)/host_sanitize_check $(LIB)/leaf_forms_check $(LIB)/launch_plan_check oracle
+all: $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer $(LIB)/fp_exhaustive $(LIB)/host_sanitize_check $(LIB)/leaf_forms_check $(LIB)/launch_plan_check $(LIB)/ctx_state_check oracle
 
 $(LIB):
 	mkdir -p $(LIB)
@@ -73,6 +74,12 @@ leafcheck: $(LIB)/leaf_forms_check
 $(LIB)/launch_plan_check: tools/launch_plan_check.cpp $(SRC)/pt_launch_plan.h $(SRC)/pt_builds.h | $(LIB)
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	  -o $@ tools/launch_plan_check.cpp
+
+# Host view of the state a context carries between calls (csrc/pt_ctx_state.h) under ASan/UBSan; run by
+# tests/test_ctx_state.py.
+$(LIB)/ctx_state_check: tools/ctx_state_check.cpp $(SRC)/pt_ctx_state.h $(SRC)/pt_launch_plan.h $(SRC)/pt_builds.h include/pt_hip.h | $(LIB)
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	  -o $@ tools/ctx_state_check.cpp
 
 clean:
 	rm -f $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer

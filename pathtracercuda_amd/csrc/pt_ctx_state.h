@@ -1,0 +1,157 @@
+// pt_ctx_state.h -- what a context carries from one call to the next, and every rule that moves it:
+// no HIP call, no context, plain values.  The C ABI functions (pt_kernels.hip, pt_denoise.h) raise the
+// events below and ask the predicates; they assign none of these fields themselves.
+// tools/ctx_state_check.cpp and tests/test_ctx_state.py run the same functions on the CPU.
+//
+// The facts, what each means and which events end it (DESIGN.md 5.8 has the host layer's flags):
+//   order           the tile cost order (pt_launch_plan.h).  `stale`: it is not of this scene, textures,
+//                   camera and schedule -- set by each of those changing and when its buffers are
+//                   replaced or it is dropped, cleared when a launch sorts it.  Scheduling only.
+//   stateEpoch      counts the changes of what a sample depends on besides the camera: scene, a texture,
+//                   a changed sky, an RNG write, an adaptive render.  Never decreases.
+//   launched, lastCam, lastState
+//                   the camera and stateEpoch of the last render: the key of a run-ahead stash.
+//   aheadValid      the last render made a run-ahead stash.  Every render and every adaptive render
+//                   consumes or drops it; the next render uses it only under the same key.
+//   aheadMisses     consecutive renders whose key had changed (at most 1000); from 2 on plan_launch
+//                   stops making stashes.
+//   adCountsValid   "the counts describe the buffer": set when an adaptive render is done, ended only by
+//                   a launch that writes the accumulation (a render, the next adaptive render).  The
+//                   adaptive reads, pt_denoise's per-pixel division and Pathtracer::adaptive() follow it.
+//   adMomValid      "the moments can be continued": the former, and also ended by a scene, texture or
+//                   sky change and an RNG write.  Implies adCountsValid; only reset = 0 asks for it.
+//   featValid       the feature planes are of the current scene and textures: set when a features call
+//                   is done, ended by its beginning and by a scene or texture change.
+//   dnValid         a denoised image is held: ended when a denoise has passed its checks, set when it is
+//                   done, so only a denoise that fails midway (a HIP error) leaves none.
+//   epoch           counts the launches that wrote the accumulation (a device group's gather cache
+//                   key, pt_group.h).  Never decreases.
+// A call refused for its arguments or for the state raises no event (but for a render whose plan is a
+// refusal: DESIGN.md 8).
+#pragma once
+#include <cstring>
+
+#include "../../include/pt_hip.h"
+#include "pt_launch_plan.h"
+
+namespace pt {
+
+struct CtxState {
+    OrderState order;
+    uint64_t stateEpoch = 0, lastState = 0;
+    bool launched = false;
+    pt_camera lastCam = {};
+    bool aheadValid = false;
+    uint32_t aheadMisses = 0;
+    bool adMomValid = false, adCountsValid = false;
+    bool featValid = false, dnValid = false;
+    uint64_t epoch = 0;
+};
+
+// ---- events ---------------------------------------------------------------------------------------
+// pt_set_scene, pt_set_texture
+inline void scene_or_texture_changed(CtxState& s)
+{
+    s.order.stale = true;
+    s.adMomValid = false;
+    s.featValid = false;
+    ++s.stateEpoch;
+}
+
+// pt_set_skybox while `held` is set: only another handle changes anything (the planes hold first hits: no
+// sky in them)
+inline void sky_set(CtxState& s, uint32_t held, uint32_t handle)
+{
+    if (held == handle) return;
+    ++s.stateEpoch;
+    s.adMomValid = false;
+}
+
+// pt_write_rng: a stash and the moments continue the old streams
+inline void rng_written(CtxState& s)
+{
+    ++s.stateEpoch;
+    s.adMomValid = false;
+}
+
+inline void schedule_changed(CtxState& s) { s.order.stale = true; }
+
+// the launch's K differs from the order's (LaunchPlan::dropOrder)
+inline void order_dropped(CtxState& s)
+{
+    s.order.valid = false;
+    s.order.stale = true;
+}
+
+// the order's buffers are replaced by ones of another size
+inline void order_replaced(CtxState& s) { order_dropped(s); }
+
+// the order was sorted from the tile costs of a launch of `samples` per pixel in units of `strip` tiles
+inline void order_sorted(CtxState& s, uint64_t samples, uint32_t strip)
+{
+    s.order.samples = samples;
+    s.order.strip = strip;
+    s.order.valid = true;
+    s.order.stale = false;
+}
+
+// those costs were measured under issue priority: the next launch rebuilds the order whatever it samples
+inline void order_biased(CtxState& s) { s.order.samples = 0; }
+
+// A render begins under `cam`.  The stash of the previous render matches when this one has its camera,
+// scene, textures, sky and RNG state.
+struct RenderStart {
+    bool stashMatches;
+    uint32_t aheadMisses;
+};
+inline RenderStart render_begins(CtxState& s, const pt_camera& cam)
+{
+    s.adMomValid = false;                 // the moments and counts of an adaptive render no longer describe the buffer
+    s.adCountsValid = false;
+    const bool sameCam = memcmp(&s.lastCam, &cam, sizeof(pt_camera)) == 0;
+    const bool sameKey = s.launched && sameCam && s.lastState == s.stateEpoch;
+    s.aheadMisses = sameKey ? 0u : std::min(s.aheadMisses + 1u, 1000u);
+    const bool stashMatches = s.aheadValid && sameKey;
+    s.aheadValid = false;                 // consumed or dropped; a making launch sets it again
+    s.launched = true;
+    s.lastState = s.stateEpoch;
+    if (!sameCam) {
+        s.order.stale = true;
+        s.lastCam = cam;
+    }
+    return {stashMatches, s.aheadMisses};
+}
+
+inline void accum_written(CtxState& s) { ++s.epoch; }
+
+inline void stash_made(CtxState& s) { s.aheadValid = true; }
+
+// the accumulation and the RNG streams move on: a stash of the old state is void; the cost order and
+// the tile costs stay as they were (an adaptive render dispatches no tiles)
+inline void adaptive_begins(CtxState& s)
+{
+    s.aheadValid = false;
+    ++s.stateEpoch;
+    accum_written(s);
+    s.adMomValid = false;                 // until the render is complete
+    s.adCountsValid = false;
+}
+
+inline void adaptive_done(CtxState& s)
+{
+    s.adMomValid = true;
+    s.adCountsValid = true;
+}
+
+inline void features_begin(CtxState& s) { s.featValid = false; }
+inline void features_done(CtxState& s) { s.featValid = true; }
+inline void denoise_begins(CtxState& s) { s.dnValid = false; }
+inline void denoise_done(CtxState& s) { s.dnValid = true; }
+
+// ---- predicates -----------------------------------------------------------------------------------
+inline bool counts_describe_buffer(const CtxState& s) { return s.adCountsValid; }
+inline bool moments_continue(const CtxState& s) { return s.adMomValid; }
+inline bool planes_current(const CtxState& s) { return s.featValid; }
+inline bool holds_denoised(const CtxState& s) { return s.dnValid; }
+
+} // namespace pt

@@ -89,7 +89,7 @@ PT_API int pt_render_features(pt_context* ctx, const pt_camera* camera)
     if (!ctx->nodes || ctx->primCount == 0) return fail(ctx, PT_ERR_STATE, "pt_render_features: no scene is set");
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->rows * ctx->width;
-    ctx->featValid = false;
+    features_begin(ctx->st);
     if (!ctx->feat) PT_HIP_CHECK(ctx, hipMalloc(&ctx->feat, 3 * std::max(npix, (size_t)1) * sizeof(float4)));
     ctx->featMs = 0.0f;
     if (npix) {
@@ -122,7 +122,7 @@ PT_API int pt_render_features(pt_context* ctx, const pt_camera* camera)
         PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->featMs, ctx->ev0, ctx->ev1));
     }
-    ctx->featValid = true;
+    features_done(ctx->st);
     return PT_OK;
 }
 
@@ -130,7 +130,7 @@ PT_API int pt_read_features(pt_context* ctx, uint32_t plane, float* dst)
 {
     if (!ctx || !dst) return PT_ERR_ARG;
     if (plane > 2u) return fail(ctx, PT_ERR_ARG, "pt_read_features: plane must be 0, 1 or 2");
-    if (!ctx->featValid)
+    if (!planes_current(ctx->st))
         return fail(ctx, PT_ERR_STATE, "pt_read_features: no feature planes (no pt_render_features since the scene or a texture was set)");
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -142,7 +142,7 @@ PT_API int pt_read_features(pt_context* ctx, uint32_t plane, float* dst)
 PT_API int pt_read_features_timing(pt_context* ctx, float* dst)
 {
     if (!ctx || !dst) return PT_ERR_ARG;
-    if (!ctx->featValid) return fail(ctx, PT_ERR_STATE, "pt_read_features_timing: no feature planes");
+    if (!planes_current(ctx->st)) return fail(ctx, PT_ERR_STATE, "pt_read_features_timing: no feature planes");
     *dst = ctx->featMs;
     return PT_OK;
 }
@@ -154,11 +154,11 @@ PT_API int pt_denoise(pt_context* ctx, uint32_t frames, const pt_denoise_params*
     if (ctx->rows != ctx->height)
         return fail(ctx, PT_ERR_ARG, "pt_denoise: the context holds a band partition, not the whole frame "
                                      "(gather the frame and use pt_denoise_image)");
-    if (!ctx->featValid)
+    if (!planes_current(ctx->st))
         return fail(ctx, PT_ERR_STATE, "pt_denoise: no feature planes (no pt_render_features since the scene or a texture was set)");
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->rows * ctx->width;
-    ctx->dnValid = false;
+    denoise_begins(ctx->st);
     if (!ctx->dnBuf) {
         PT_HIP_CHECK(ctx, hipMalloc(&ctx->dnBuf, 6 * npix * sizeof(float4)));   // colour, g0, g1, ping, pong, out
         for (auto& e : ctx->dnEv) PT_HIP_CHECK(ctx, hipEventCreate(&e));
@@ -166,7 +166,7 @@ PT_API int pt_denoise(pt_context* ctx, uint32_t frames, const pt_denoise_params*
     float4* color = ctx->dnBuf;
     const float inv = 1.0f / fmaxf((float)frames, 1.0f);
     dn_color_kernel<<<(unsigned)((npix + 255) / 256), 256, 0, ctx->stream>>>(
-        color, ctx->accum, ctx->adCountsValid ? ctx->adMom + 2 * npix : nullptr, npix, inv);
+        color, ctx->accum, counts_describe_buffer(ctx->st) ? ctx->adMom + 2 * npix : nullptr, npix, inv);
     PT_HIP_CHECK(ctx, hipGetLastError());
     PT_HIP_CHECK(ctx, denoise_run(ctx->stream, *params, ctx->width, ctx->height, color, ctx->feat, ctx->dnBuf + npix,
                                   ctx->dnBuf + 2 * npix, ctx->dnBuf + 3 * npix, ctx->dnBuf + 4 * npix,
@@ -177,14 +177,14 @@ PT_API int pt_denoise(pt_context* ctx, uint32_t frames, const pt_denoise_params*
     for (uint32_t i = 0; i < params->iterations; ++i)
         PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[1 + i], ctx->dnEv[1 + i], ctx->dnEv[2 + i]));
     PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[9], ctx->dnEv[1 + params->iterations], ctx->dnEv[11]));
-    ctx->dnValid = true;
+    denoise_done(ctx->st);
     return PT_OK;
 }
 
 PT_API int pt_read_denoise_timing(pt_context* ctx, float* dst)
 {
     if (!ctx || !dst) return PT_ERR_ARG;
-    if (!ctx->dnValid) return fail(ctx, PT_ERR_STATE, "pt_read_denoise_timing: no denoised image");
+    if (!holds_denoised(ctx->st)) return fail(ctx, PT_ERR_STATE, "pt_read_denoise_timing: no denoised image");
     for (int k = 0; k < 10; ++k) dst[k] = ctx->dnMs[k];
     return PT_OK;
 }
@@ -192,7 +192,7 @@ PT_API int pt_read_denoise_timing(pt_context* ctx, float* dst)
 PT_API int pt_read_denoised(pt_context* ctx, float* dst)
 {
     if (!ctx || !dst) return PT_ERR_ARG;
-    if (!ctx->dnValid) return fail(ctx, PT_ERR_STATE, "pt_read_denoised: no denoised image (no pt_denoise yet)");
+    if (!holds_denoised(ctx->st)) return fail(ctx, PT_ERR_STATE, "pt_read_denoised: no denoised image (no pt_denoise yet)");
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     const size_t npix = (size_t)ctx->rows * ctx->width;
@@ -203,7 +203,7 @@ PT_API int pt_read_denoised(pt_context* ctx, float* dst)
 PT_API int pt_tonemap_denoised(pt_context* ctx, uint8_t* dst)
 {
     if (!ctx || !dst) return PT_ERR_ARG;
-    if (!ctx->dnValid) return fail(ctx, PT_ERR_STATE, "pt_tonemap_denoised: no denoised image (no pt_denoise yet)");
+    if (!holds_denoised(ctx->st)) return fail(ctx, PT_ERR_STATE, "pt_tonemap_denoised: no denoised image (no pt_denoise yet)");
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->rows * ctx->width;
     if (!ctx->ldr) PT_HIP_CHECK(ctx, hipMalloc(&ctx->ldr, npix * sizeof(uchar4)));

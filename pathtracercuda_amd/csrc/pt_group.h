@@ -29,7 +29,7 @@ static bool group_gathered(const pt_group* g)
 {
     if (g->gatherEpoch.size() != g->ctx.size()) return false;
     for (size_t i = 0; i < g->ctx.size(); ++i)
-        if (g->gatherEpoch[i] != g->ctx[i]->epoch) return false;
+        if (g->gatherEpoch[i] != g->ctx[i]->st.epoch) return false;
     return true;
 }
 
@@ -193,7 +193,7 @@ PT_API int pt_group_gather(pt_group* g, float* host_ms)
         PT_GHIP_CHECK(g, hipStreamSynchronize(g->ctx[i]->stream));
     }
     g->gatherEpoch.clear();
-    for (pt_context* c : g->ctx) g->gatherEpoch.push_back(c->epoch);
+    for (pt_context* c : g->ctx) g->gatherEpoch.push_back(c->st.epoch);
     if (host_ms) *host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PT_OK;
 }

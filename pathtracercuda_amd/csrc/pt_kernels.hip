@@ -39,6 +39,7 @@
 #include "pt_math.h"
 #include "pt_leaf_forms.h"
 #include "pt_launch_plan.h"
+#include "pt_ctx_state.h"
 #include "../../include/pt_hip.h"
 
 using namespace pt;
@@ -493,15 +494,8 @@ struct pt_context {
     uint32_t cnodeCount = 0, rootWord = 0;
     bool dfsOrder = true;             // leaves hold their primitives in DFS order (repair_pending)
     int zeroConstsType = -1;          // pt_set_zero_quadric_consts (tests' negative control only)
-    // run-ahead across render() calls (MODE 4): the stash and the key it was made under
-    uint32_t* ahead = nullptr;        // [kAheadWords][pixels]
-    bool aheadValid = false;          // the last launch made a stash
-    pt_camera aheadCam = {};
-    uint64_t aheadState = 0;          // stateEpoch when it was made
-    uint32_t aheadMisses = 0;         // consecutive launches that could not use the previous stash
-    uint64_t stateEpoch = 0;          // bumped by every change of scene, textures, sky or RNG state
-    uint64_t lastState = 0;           // stateEpoch at the last launch
-    bool launched = false;
+    CtxState st;                      // what one call leaves for the next: every validity flag (pt_ctx_state.h)
+    uint32_t* ahead = nullptr;        // run-ahead across render() calls (MODE 4): the stash, [kAheadWords][pixels]
     float rootBox[6] = {};
     uint32_t nodeCount = 0, primCount = 0, stackDepth = 1;
     bool slabFast = true;
@@ -526,7 +520,6 @@ struct pt_context {
     size_t sortTempBytes = 0;
     uchar4* ldr = nullptr;        // tonemap staging buffer (pt_tonemap)
     uint32_t orderTiles = 0;      // tiles the device buffers hold
-    OrderState orderState;        // of `order` (pt_launch_plan.h)
     uint32_t* unitMajor = nullptr;    // row-major order of strip units (packed first tiles), for unitK
     uint32_t unitK = 0, unitTiles = 0;
     uint32_t occupancy = 0;       // tuning knob: workgroups per CU of persistent grids (0 = all that fit)
@@ -534,7 +527,6 @@ struct pt_context {
     uint32_t patchRounds = 6;     // patch rounds before the remaining dead ends run plain
     uint32_t ssgLook[2] = {64, 16}; // second-phase lag tolerances in samples (TraceParams::ssgLook)
     float* pairs = nullptr;       // per-pixel draw pairs per sample (start-offset guesses)
-    bool pairsValid = false;
     uint32_t* ssgStart = nullptr;
     unsigned long long* ssgBits = nullptr;
     uint32_t* ssgCount = nullptr;
@@ -552,8 +544,6 @@ struct pt_context {
     uint32_t groupStats[10] = {}; // G, patch rounds, dead-end pixels after fold rounds 0..7
     // adaptive sampling (pt_render_adaptive): per-pixel moments and the compaction buffers
     uint32_t* adMom = nullptr;        // [3][pixels]: m1, m2 (float bits), n
-    bool adMomValid = false;          // the moments can be continued (reset = 0): scene, textures, sky and RNG are theirs
-    bool adCountsValid = false;       // the per-pixel counts describe the accumulation buffer (the adaptive reads)
     uint32_t adSteps = 0;             // steps (calls of the active pixels) made since the last reset
     uint8_t* adFlag = nullptr;        // [pixels] has its minimum of calls and is not converged
     unsigned long long* adMasks = nullptr;   // [tiles] ballot of the tile's active pixels
@@ -564,14 +554,10 @@ struct pt_context {
     size_t adTempBytes = 0;
     // first-hit feature planes and the denoiser (pt_denoise.h); no render state
     float4* feat = nullptr;           // [3][pixels], allocated by the first pt_render_features
-    bool featValid = false;           // the planes describe the current scene and textures
     float featMs = 0.0f;
     float4* dnBuf = nullptr;          // [6][pixels]: colour, two guide planes, two iteration buffers, the result
-    bool dnValid = false;             // dnBuf holds a denoised image
     hipEvent_t dnEv[12] = {};
     float dnMs[10] = {};
-    pt_camera lastCam = {};
-    uint64_t epoch = 0;           // launches that wrote the accumulation (a group's gather cache key)
     std::string err;
 };
 
@@ -1033,10 +1019,7 @@ PT_API int pt_set_scene(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node
         ctx->cnodeCount = interior;
     }
     ctx->dfsOrder = dfsOrder;
-    ctx->orderState.stale = true;
-    ctx->adMomValid = false;
-    ctx->featValid = false;
-    ++ctx->stateEpoch;
+    scene_or_texture_changed(ctx->st);
     ctx->rootWord = word(0);
     for (int k = 0; k < 3; ++k) {
         ctx->rootBox[2 * k] = nodes[0].aabb_min[k];
@@ -1094,10 +1077,7 @@ PT_API int pt_set_texture(pt_context* ctx, uint32_t handle, const float* rgba, u
     t.height = height;
     t.fwidth = (float)width;
     t.fheight = (float)height;
-    ctx->orderState.stale = true;
-    ctx->adMomValid = false;
-    ctx->featValid = false;
-    ++ctx->stateEpoch;
+    scene_or_texture_changed(ctx->st);
     PT_HIP_CHECK(ctx, hipMemcpy(ctx->texTable, ctx->hostTex, sizeof(ctx->hostTex), hipMemcpyHostToDevice));
     return PT_OK;
 }
@@ -1106,10 +1086,7 @@ PT_API int pt_set_skybox(pt_context* ctx, uint32_t handle)
 {
     if (!ctx) return PT_ERR_ARG;
     if (handle > PT_MAX_TEXTURES) return fail(ctx, PT_ERR_ARG, "pt_set_skybox: invalid handle");
-    if (ctx->skybox != handle) {
-        ++ctx->stateEpoch;
-        ctx->adMomValid = false;
-    }
+    sky_set(ctx->st, ctx->skybox, handle);
     ctx->skybox = handle;
     return PT_OK;
 }
@@ -1200,14 +1177,11 @@ static void ssg_release(pt_context* ctx)
 // in tile order.
 static int sort_order(pt_context* ctx, uint32_t tiles, uint64_t samples, uint32_t strip)
 {
-    ctx->orderState.samples = samples;
-    ctx->orderState.strip = strip;
     size_t bytes = ctx->sortTempBytes;
     PT_HIP_CHECK(ctx, rocprim::radix_sort_pairs_desc(ctx->sortTemp, bytes, ctx->tileCost, ctx->sortKeys, ctx->tileIds,
                                                      ctx->order, tiles, 0, 32, ctx->stream));
     PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->orderState.valid = true;
-    ctx->orderState.stale = false;
+    order_sorted(ctx->st, samples, strip);
     return PT_OK;
 }
 
@@ -1243,7 +1217,6 @@ static int run_groups(pt_context* ctx, int variant, const TraceParams& P0, uint3
     ssg_fold_kernel<<<pixBlocks, 256, 0, s>>>(P, 0, ctx->patchLog, ctx->patchEnd, ctx->patchCount, ssgCap, ctx->pairs,
                                               ctx->deadCount);
     PT_HIP_CHECK(ctx, hipGetLastError());
-    ctx->pairsValid = true;
     // Patch rounds: a carrier from each dead end (the exact state there) runs until it meets a
     // later group's parse, and the fold continues; what is left after them runs plain.
     TraceParams Q = P;
@@ -1352,7 +1325,7 @@ static int order_reserve(pt_context* ctx, uint32_t tilesX, uint32_t tilesY)
     ctx->order = nullptr;
     ctx->tileIdle = nullptr;
     ctx->orderTiles = 0;
-    ctx->orderState.valid = false;
+    order_replaced(ctx->st);
     PT_HIP_CHECK(ctx, hipMalloc(&ctx->tileCost, (size_t)tiles * sizeof(uint32_t)));
     PT_HIP_CHECK(ctx, hipMalloc(&ctx->order, ((size_t)tiles + 64) * sizeof(uint32_t)));
     (void)hipFree(ctx->sortKeys);
@@ -1379,7 +1352,6 @@ static int order_reserve(pt_context* ctx, uint32_t tilesX, uint32_t tilesY)
     PT_HIP_CHECK(ctx, hipMemcpy(ctx->order, ident.data(), ident.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     PT_HIP_CHECK(ctx, hipMemcpy(ctx->tileIds, ident.data(), (size_t)tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
     ctx->orderTiles = tiles;
-    ctx->orderState.stale = true;
     return PT_OK;
 }
 
@@ -1408,13 +1380,10 @@ static void set_priority(TraceParams& P, const PassPriority& pp)
 
 // Execute a plan (pt_launch_plan.h): the buffers it needs, the cold-start pass, the main pass, the
 // order's rebuild.  P holds base_params.
-static int run_plan(pt_context* ctx, const pt_camera* cam, const LaunchInputs& in, LaunchPlan plan, TraceParams P,
-                    float* gpu_ms, pt_render_stats* stats)
+static int run_plan(pt_context* ctx, const LaunchInputs& in, LaunchPlan plan, TraceParams P, float* gpu_ms,
+                    pt_render_stats* stats)
 {
-    if (plan.dropOrder) {
-        ctx->orderState.valid = false;
-        ctx->orderState.stale = true;
-    }
+    if (plan.dropOrder) order_dropped(ctx->st);
     if (plan.refusal) return fail(ctx, PT_ERR_STATE, plan.refusal);
     const uint32_t tiles = P.tilesX * P.tilesY, K = plan.K, total = P.spp * P.chunks, chunks = P.chunks;
     const bool sorted = ctx->knobs.schedule == 0;
@@ -1458,7 +1427,7 @@ static int run_plan(pt_context* ctx, const pt_camera* cam, const LaunchInputs& i
     ctx->lastGroups = 0;
     ctx->lastVariant = plan.build;
     memset(ctx->groupStats, 0, sizeof(ctx->groupStats));
-    ++ctx->epoch;
+    accum_written(ctx->st);
     if (plan.G) {
         const size_t J = 2 * (size_t)plan.G - 1;
         if (!ssg_reserve(ctx, tiles, (size_t)tiles * J, (size_t)tiles * J * plan.ssgCap, (size_t)tiles * plan.ssgCap,
@@ -1484,7 +1453,6 @@ static int run_plan(pt_context* ctx, const pt_camera* cam, const LaunchInputs& i
             Q.ignoreFirst = 1;
             Q.discard = 1;
             Q.pairsOut = plan.coldPairs && ssg_reserve(ctx, tiles, 0, 0, 0) ? ctx->pairs : nullptr;
-            if (Q.pairsOut) ctx->pairsValid = true;
         }
         PT_HIP_CHECK(ctx, Q.pairsOut ? launch_build<false, kModeAux>(plan.build, Q, ctx->cus, ctx->stream)
                           : K > 1    ? launch_resumable(plan.build, kModeStrip, Q, ctx->cus, ctx->stream)
@@ -1508,11 +1476,7 @@ static int run_plan(pt_context* ctx, const pt_camera* cam, const LaunchInputs& i
                                                            : launch_build<false, kModePlain>(plan.build, P, ctx->cus, ctx->stream));
     }
     memcpy(ctx->lastLaunch, g_lastLaunch, sizeof(ctx->lastLaunch));
-    if (plan.aheadMake) {
-        ctx->aheadValid = true;
-        ctx->aheadCam = *cam;
-        ctx->aheadState = ctx->stateEpoch;
-    }
+    if (plan.aheadMake) stash_made(ctx->st);
     PT_HIP_CHECK(ctx, hipGetLastError());
     PT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     PT_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
@@ -1522,7 +1486,7 @@ static int run_plan(pt_context* ctx, const pt_camera* cam, const LaunchInputs& i
     if (plan.rebuildOrder) {
         const int rs = sort_order(ctx, tiles, total, K);
         if (rs != PT_OK) return rs;
-        if (plan.biasedOrder) ctx->orderState.samples = 0;
+        if (plan.biasedOrder) order_biased(ctx->st);
     }
     if (stats) {
         static_assert(sizeof(pt_render_stats) == kStatWords * sizeof(uint64_t), "the counters in the order of pt_render_stats");
@@ -1545,24 +1509,10 @@ static int render_impl(pt_context* ctx, const pt_camera* cam, uint32_t spp, uint
         return fail(ctx, PT_ERR_STATE, "pt_render: skybox handle has no texture");
     TraceParams P;
     base_params(ctx, cam, spp, chunks, ignore, P);
-    ctx->adMomValid = false;              // the moments and counts of an adaptive render no longer describe the buffer
-    ctx->adCountsValid = false;
+    const RenderStart begun = render_begins(ctx->st, *cam);
     int rc = order_reserve(ctx, P.tilesX, P.tilesY);
     if (rc == PT_OK) rc = cursor_reserve(ctx);
     if (rc != PT_OK) return rc;
-    // A run-ahead stash made by the previous launch is valid when this launch has its camera, scene,
-    // textures, sky and RNG state (stateEpoch).
-    const bool sameCam = memcmp(&ctx->lastCam, cam, sizeof(pt_camera)) == 0;
-    const bool sameKey = ctx->launched && sameCam && ctx->lastState == ctx->stateEpoch;
-    ctx->aheadMisses = sameKey ? 0u : std::min(ctx->aheadMisses + 1u, 1000u);
-    const bool stashMatches = ctx->aheadValid && sameKey;
-    ctx->aheadValid = false;              // consumed or dropped; a making launch sets it again
-    ctx->launched = true;
-    ctx->lastState = ctx->stateEpoch;
-    if (!sameCam) {
-        ctx->orderState.stale = true;
-        ctx->lastCam = *cam;
-    }
     LaunchInputs in = {};
     in.cus = (uint32_t)ctx->cus;
     in.tilesX = P.tilesX;
@@ -1572,10 +1522,10 @@ static int render_impl(pt_context* ctx, const pt_camera* cam, uint32_t spp, uint
     in.instrumented = stats != nullptr;
     in.scene = scene_facts(ctx);
     in.knobs = ctx->knobs;
-    in.order = ctx->orderState;
-    in.stashMatches = stashMatches;
-    in.aheadMisses = ctx->aheadMisses;
-    return run_plan(ctx, cam, in, plan_launch(in), P, gpu_ms, stats);
+    in.order = ctx->st.order;
+    in.stashMatches = begun.stashMatches;
+    in.aheadMisses = begun.aheadMisses;
+    return run_plan(ctx, in, plan_launch(in), P, gpu_ms, stats);
 }
 
 PT_API int pt_set_cold_start(pt_context* ctx, uint32_t prepass_spp, int priority)
@@ -1703,7 +1653,7 @@ PT_API int pt_set_schedule(pt_context* ctx, int mode)
 {
     if (!ctx || mode < 0 || mode > 2) return PT_ERR_ARG;
     ctx->knobs.schedule = mode;
-    ctx->orderState.stale = true;
+    schedule_changed(ctx->st);
     return PT_OK;
 }
 
@@ -1777,7 +1727,7 @@ PT_API int pt_render_adaptive(pt_context* ctx, const pt_camera* camera, const pt
     if (ctx->nodeCount < 1 || ctx->primCount < 1) return fail(ctx, PT_ERR_STATE, "pt_render_adaptive: no scene set");
     if (ctx->skybox != 0 && ctx->hostTex[ctx->skybox - 1].texels == nullptr)
         return fail(ctx, PT_ERR_STATE, "pt_render_adaptive: skybox handle has no texture");
-    if (!ap.reset && !ctx->adMomValid)
+    if (!ap.reset && !moments_continue(ctx->st))
         return fail(ctx, PT_ERR_STATE, "pt_render_adaptive: reset = 0 needs the moments of an adaptive render; there has been "
                                        "none since the last plain render, RNG write or scene, texture or sky change");
     const int variant = picked_build(ctx->knobs.variant, scene_facts(ctx));
@@ -1795,13 +1745,7 @@ PT_API int pt_render_adaptive(pt_context* ctx, const pt_camera* camera, const pt
     P.occCap = ctx->occupancy;
     P.adList = ctx->adList;
     P.adMom = ctx->adMom;
-    // the accumulation and the RNG streams move on: a run-ahead stash of the old state is void; the
-    // cost order and the tile costs stay as they were (this path dispatches no tiles)
-    ctx->aheadValid = false;
-    ++ctx->stateEpoch;
-    ++ctx->epoch;
-    ctx->adMomValid = false;              // until the render is complete
-    ctx->adCountsValid = false;
+    adaptive_begins(ctx->st);
     ctx->lastGroups = 0;
     ctx->lastVariant = variant;
     PT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -1841,8 +1785,7 @@ PT_API int pt_render_adaptive(pt_context* ctx, const pt_camera* camera, const pt
     PT_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
     float ms = 0.0f;
     PT_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->adMomValid = true;
-    ctx->adCountsValid = true;
+    adaptive_done(ctx->st);
     if (result) {
         result->rounds = rounds;
         result->samples = samples;
@@ -1851,12 +1794,12 @@ PT_API int pt_render_adaptive(pt_context* ctx, const pt_camera* camera, const pt
     return PT_OK;
 }
 
-PT_API int pt_holds_adaptive(const pt_context* ctx) { return ctx && ctx->adCountsValid ? 1 : 0; }
+PT_API int pt_holds_adaptive(const pt_context* ctx) { return ctx && counts_describe_buffer(ctx->st) ? 1 : 0; }
 
 PT_API int pt_read_moments(pt_context* ctx, float* dst)
 {
     if (!ctx || !dst) return PT_ERR_ARG;
-    if (!ctx->adCountsValid) return fail(ctx, PT_ERR_STATE, "pt_read_moments: no adaptive render describes the buffer");
+    if (!counts_describe_buffer(ctx->st)) return fail(ctx, PT_ERR_STATE, "pt_read_moments: no adaptive render describes the buffer");
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     const size_t npix = (size_t)ctx->rows * ctx->width;
@@ -1870,7 +1813,7 @@ PT_API int pt_read_moments(pt_context* ctx, float* dst)
 PT_API int pt_read_adaptive_hdr(pt_context* ctx, float* dst)
 {
     if (!ctx || !dst) return PT_ERR_ARG;
-    if (!ctx->adCountsValid) return fail(ctx, PT_ERR_STATE, "pt_read_adaptive_hdr: no adaptive render describes the buffer");
+    if (!counts_describe_buffer(ctx->st)) return fail(ctx, PT_ERR_STATE, "pt_read_adaptive_hdr: no adaptive render describes the buffer");
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     const size_t npix = (size_t)ctx->rows * ctx->width;
@@ -1887,7 +1830,7 @@ PT_API int pt_read_adaptive_hdr(pt_context* ctx, float* dst)
 PT_API int pt_tonemap_adaptive(pt_context* ctx, uint8_t* dst)
 {
     if (!ctx || !dst) return PT_ERR_ARG;
-    if (!ctx->adCountsValid) return fail(ctx, PT_ERR_STATE, "pt_tonemap_adaptive: no adaptive render describes the buffer");
+    if (!counts_describe_buffer(ctx->st)) return fail(ctx, PT_ERR_STATE, "pt_tonemap_adaptive: no adaptive render describes the buffer");
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->rows * ctx->width;
     if (npix == 0) return PT_OK;
@@ -1971,8 +1914,7 @@ PT_API int pt_write_rng(pt_context* ctx, const uint32_t* src)
     for (size_t i = 0; i < npix; ++i)
         for (int k = 0; k < 6; ++k) soa[k * npix + i] = src[6 * i + k];
     PT_HIP_CHECK(ctx, hipMemcpy(ctx->rng, soa.data(), soa.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    ++ctx->stateEpoch;                    // a run-ahead stash continues the old streams: void
-    ctx->adMomValid = false;
+    rng_written(ctx->st);
     return PT_OK;
 }
 

@@ -1,0 +1,170 @@
+// Host view of what a context carries between calls (pathtracercuda_amd/csrc/pt_ctx_state.h), for
+// tests/test_ctx_state.py.
+//   g++ -O1 -std=c++17 -fsanitize=address,undefined -o ctx_state_check tools/ctx_state_check.cpp
+// Reads one request per line on stdin and prints the whole state as one JSON object per request (flushed,
+// so a test can decide its next request from the answer):
+//   new                         a fresh context's state
+//   <event> [key=value ...]     an event of the header by name; render_begins takes cam=ID (a small integer
+//                               the tool turns into distinct pt_camera bytes) and adds "stashMatches" and
+//                               "misses" to the object, order_sorted takes samples= and strip=, sky_set takes held= and
+//                               handle=
+//   <predicate>                 a predicate of the header by name; adds "result"
+//   fuzz seed=S n=N             N seeded random events on a fresh state; adds "violations", the number of
+//                               times one of the invariants of Fuzz::step did not hold
+// Exit status 0 = every request understood.
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+#include <sstream>
+#include <string>
+
+#include "../pathtracercuda_amd/csrc/pt_ctx_state.h"
+
+using namespace pt;
+
+typedef std::map<std::string, unsigned long long> Row;
+
+static unsigned long long get(Row& r, const char* key, unsigned long long dflt)
+{
+    auto it = r.find(key);
+    if (it == r.end()) return dflt;
+    const unsigned long long v = it->second;
+    r.erase(it);
+    return v;
+}
+
+static pt_camera camera_of(unsigned long long id)
+{
+    pt_camera c = {};
+    c.origin[0] = (float)id;
+    return c;
+}
+
+static void (*const kEventFns[])(CtxState&) = {
+    scene_or_texture_changed, rng_written, schedule_changed, order_dropped, order_replaced, order_biased,
+    accum_written, stash_made, adaptive_begins, adaptive_done, features_begin, features_done, denoise_begins, denoise_done};
+static const char* const kEventNames[] = {
+    "scene_or_texture_changed", "rng_written", "schedule_changed", "order_dropped", "order_replaced",
+    "order_biased", "accum_written", "stash_made", "adaptive_begins", "adaptive_done", "features_begin", "features_done",
+    "denoise_begins", "denoise_done"};
+constexpr int kEvents = sizeof(kEventFns) / sizeof(kEventFns[0]);
+// the tool's own list of the events after which a sample is no longer what the last render's was
+static bool moves_epoch(void (*event)(CtxState&))
+{
+    return event == scene_or_texture_changed || event == rng_written || event == adaptive_begins;
+}
+static_assert(kEvents == sizeof(kEventNames) / sizeof(kEventNames[0]), "one name per event");
+
+static bool (*const kPredicates[])(const CtxState&) = {counts_describe_buffer, moments_continue, planes_current, holds_denoised};
+static const char* const kPredicateNames[] = {"counts_describe_buffer", "moments_continue", "planes_current", "holds_denoised"};
+
+// The tool's own account of the stash, kept beside the state: a stash matches exactly when the previous
+// render made one, this render has that render's camera id, and no epoch-moving event came in between.
+struct Shadow {
+    bool rendered = false, stash = false, moved = false;
+    unsigned long long cam = 0;
+};
+
+struct Fuzz {
+    CtxState s;
+    Shadow sh;
+    uint64_t rng;
+    unsigned long long violations = 0;
+
+    uint32_t next()                     // xorshift64*
+    {
+        rng ^= rng >> 12;
+        rng ^= rng << 25;
+        rng ^= rng >> 27;
+        return (uint32_t)((rng * 2685821657736338717ull) >> 32);
+    }
+    void check(bool ok) { violations += ok ? 0 : 1; }
+    void step()
+    {
+        const uint64_t stateEpoch = s.stateEpoch, epoch = s.epoch;
+        const uint32_t e = next() % (kEvents + 6);       // (a render as likely as four other events)
+        if (e < (uint32_t)kEvents) {
+            kEventFns[e](s);
+            if (kEventFns[e] == stash_made) sh.stash = sh.rendered;
+            if (moves_epoch(kEventFns[e])) sh.moved = true;
+        } else if (e == (uint32_t)kEvents) {
+            order_sorted(s, next() % 4096, 1 + next() % 4);
+        } else if (e == (uint32_t)kEvents + 1) {
+            const uint32_t held = next() % 2, handle = next() % 2;
+            sky_set(s, held, handle);
+            if (held != handle) sh.moved = true;
+        } else {
+            const unsigned long long cam = next() % 3;
+            const RenderStart r = render_begins(s, camera_of(cam));
+            check(r.stashMatches == (sh.stash && !sh.moved && sh.cam == cam));
+            check(!s.aheadValid && s.launched && s.lastState == s.stateEpoch);
+            check(r.aheadMisses == s.aheadMisses);
+            sh = {true, false, false, cam};
+        }
+        check(!s.adMomValid || s.adCountsValid);
+        check(s.stateEpoch >= stateEpoch && s.epoch >= epoch);
+        check(s.aheadMisses <= 1000u);
+    }
+};
+
+static void print_state(const CtxState& s, const std::string& extra)
+{
+    printf("{\"order\": {\"valid\": %d, \"stale\": %d, \"samples\": %llu, \"strip\": %u}, \"stateEpoch\": %llu, "
+           "\"lastState\": %llu, \"launched\": %d, \"lastCam\": %d, \"aheadValid\": %d, \"aheadMisses\": %u, \"adMomValid\": %d, "
+           "\"adCountsValid\": %d, \"featValid\": %d, \"dnValid\": %d, \"epoch\": %llu%s}\n",
+           (int)s.order.valid, (int)s.order.stale, (unsigned long long)s.order.samples, s.order.strip,
+           (unsigned long long)s.stateEpoch, (unsigned long long)s.lastState, (int)s.launched, (int)s.lastCam.origin[0],
+           (int)s.aheadValid, s.aheadMisses, (int)s.adMomValid, (int)s.adCountsValid, (int)s.featValid, (int)s.dnValid,
+           (unsigned long long)s.epoch, extra.c_str());
+    fflush(stdout);
+}
+
+int main()
+{
+    CtxState s;
+    char buf[4096];
+    while (fgets(buf, sizeof(buf), stdin)) {
+        std::istringstream ss(buf);
+        std::string what, tok, extra;
+        if (!(ss >> what)) continue;
+        Row r;
+        while (ss >> tok) {
+            const size_t eq = tok.find('=');
+            if (eq == std::string::npos) {
+                fprintf(stderr, "ctx_state_check: '%s' is not key=value\n", tok.c_str());
+                return 2;
+            }
+            r[tok.substr(0, eq)] = strtoull(tok.c_str() + eq + 1, nullptr, 10);
+        }
+        bool ok = false;
+        for (int i = 0; i < kEvents && !ok; ++i)
+            if ((ok = what == kEventNames[i])) kEventFns[i](s);
+        for (int i = 0; i < 4 && !ok; ++i)
+            if ((ok = what == kPredicateNames[i])) extra = std::string(", \"result\": ") + (kPredicates[i](s) ? "1" : "0");
+        if (ok) {
+        } else if ((ok = what == "new")) {
+            s = CtxState{};
+        } else if ((ok = what == "order_sorted")) {
+            const uint64_t samples = get(r, "samples", 0);
+            order_sorted(s, samples, (uint32_t)get(r, "strip", 1));
+        } else if ((ok = what == "sky_set")) {
+            const uint32_t held = (uint32_t)get(r, "held", 0);
+            sky_set(s, held, (uint32_t)get(r, "handle", 0));
+        } else if ((ok = what == "render_begins")) {
+            const RenderStart b = render_begins(s, camera_of(get(r, "cam", 0)));
+            extra = ", \"stashMatches\": " + std::to_string((int)b.stashMatches) + ", \"misses\": " + std::to_string(b.aheadMisses);
+        } else if ((ok = what == "fuzz")) {
+            Fuzz f = {CtxState{}, {}, (get(r, "seed", 1) * 0x9e3779b97f4a7c15ull) | 1, 0};
+            for (unsigned long long n = get(r, "n", 0); n > 0; --n) f.step();
+            s = f.s;
+            extra = ", \"violations\": " + std::to_string(f.violations);
+        }
+        if (!ok || !r.empty()) {
+            fprintf(stderr, "ctx_state_check: bad request '%s'%s%s\n", what.c_str(), r.empty() ? "" : ", unknown key ",
+                    r.empty() ? "" : r.begin()->first.c_str());
+            return 2;
+        }
+        print_state(s, extra);
+    }
+    return 0;
+}
