@@ -3,6 +3,8 @@
 #   pathtracercuda_amd/lib/libpt_host.so  host C++ layer + C ABI (include/pathtracer_amd.hpp, pt_host.h)
 #   pathtracercuda_amd/lib/pathtracer     CLI (reference main.cpp headless path)
 #   pathtracercuda_amd/lib/fp_exhaustive  all-inputs check of the kernel's fast 1/x and sqrt (GPU)
+#   pathtracercuda_amd/lib/dev_functions  the kernel's device functions one by one over input files, for
+#                                         tests/test_gpu_dev_functions.py (GPU)
 #   pathtracercuda_amd/lib/host_sanitize_check  ASan/UBSan mutation check of the host parsers (CPU)
 #   pathtracercuda_amd/lib/leaf_forms_check  exact vs fast form of the cube leaf test (CPU; `make leafcheck` runs it)
 #   pathtracercuda_amd/lib/launch_plan_check  the launch policy and the build table on the host, for tests/test_launch_plan.py (CPU)
@@ -27,12 +29,14 @@ HOST_HDRS := include/pathtracer_amd.hpp include/pt_host.h include/pt_hip.h $(SRC
 # vectorizer's own pairings bound two scalars of the GGX visibility term into one register tuple
 # that the allocator then spilled around a range guard in every GGX shading.  Off: scratch 40 -> 12
 # B/lane (no spill inside the loop), +4.6 % on C3 same-box (profiles/r03_slp_ab.json).
-HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -fvisibility=hidden \
-            -mcode-object-version=5 -Iinclude -Wall -Wno-unused-result
+# HIPCODEGEN: the flags that decide how a device function compiles.  The stand-alone GPU tools take them
+# too, so that pt_math.h and the pt_dev_*.h they include compile there as they do in libpt_hip.so.
+HIPCODEGEN ?= --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -mcode-object-version=5
+HIPFLAGS ?= $(HIPCODEGEN) -fPIC -fvisibility=hidden -Iinclude -Wall -Wno-unused-result
 CXXFLAGS ?= -O2 -std=c++17 -ffp-contract=off -fno-fast-math -fPIC -Iinclude -I$(SRC)/host -Wall -Wextra \
             -Wno-unused-parameter -Wno-missing-field-initializers
 
-all: $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer $(LIB)/fp_exhaustive $(LIB)/host_sanitize_check $(LIB)/leaf_forms_check $(LIB)/launch_plan_check $(LIB)/ctx_state_check oracle
+all: $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer $(LIB)/fp_exhaustive $(LIB)/dev_functions $(LIB)/host_sanitize_check $(LIB)/leaf_forms_check $(LIB)/launch_plan_check $(LIB)/ctx_state_check oracle
 
 $(LIB):
 	mkdir -p $(LIB)
@@ -47,7 +51,11 @@ $(LIB)/pathtracer: $(SRC)/host/cli_main.cpp $(LIB)/libpt_host.so
 	$(CXX) $(CXXFLAGS) -o $@ $(SRC)/host/cli_main.cpp -L$(LIB) -lpt_host -lpt_hip -lpthread -Wl,-rpath,'$$ORIGIN'
 
 $(LIB)/fp_exhaustive: tools/fp_exhaustive.hip $(SRC)/pt_math.h | $(LIB)
-	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -o $@ tools/fp_exhaustive.hip
+	$(HIPCC) $(HIPCODEGEN) -o $@ tools/fp_exhaustive.hip
+
+# The kernel's device functions, one operation per launch, over raw input words (tools/dev_functions.hip).
+$(LIB)/dev_functions: tools/dev_functions.hip $(SRC)/pt_math.h $(SRC)/pt_dev_tex.h $(SRC)/pt_dev_tonemap.h | $(LIB)
+	$(HIPCC) $(HIPCODEGEN) -Wall -o $@ tools/dev_functions.hip
 
 oracle:
 	$(MAKE) -C oracle REF=$(REF)

@@ -1463,6 +1463,55 @@ OR_EXPORT void or_hdr_normalize(const float *accum, size_t npix, uint32_t frames
     for (size_t i = 0; i < 4 * npix; ++i) out[i] = accum[i] * inv;
 }
 
+/* Array entry points over the single operations, for tests/test_dev_inputs.py and
+ * tests/test_gpu_dev_functions.py: loops only, the arithmetic is the functions' above.  (or_tonemap
+ * already is one.)  States are written as 6 words d, v[0..4]. */
+OR_EXPORT void or_dev_sincos(const float *x, size_t n, float *s, float *c)
+{
+    for (size_t i = 0; i < n; ++i) { s[i] = pm_sinf(x[i]); c[i] = pm_cosf(x[i]); }
+}
+OR_EXPORT void or_dev_acos(const float *x, size_t n, float *out) { for (size_t i = 0; i < n; ++i) out[i] = pm_acosf(x[i]); }
+OR_EXPORT void or_dev_atan2(const float *y, const float *x, size_t n, float *out)
+{
+    for (size_t i = 0; i < n; ++i) out[i] = pm_atan2f(y[i], x[i]);
+}
+OR_EXPORT void or_dev_log(const float *x, size_t n, float *out) { for (size_t i = 0; i < n; ++i) out[i] = pm_logf(x[i]); }
+OR_EXPORT void or_dev_exp(const float *x, size_t n, float *out) { for (size_t i = 0; i < n; ++i) out[i] = pm_expf(x[i]); }
+OR_EXPORT void or_dev_pow(const float *x, const float *y, size_t n, float *out)
+{
+    for (size_t i = 0; i < n; ++i) out[i] = pm_powf(x[i], y[i]);
+}
+OR_EXPORT void or_dev_f2i(const float *x, size_t n, int32_t *out) { for (size_t i = 0; i < n; ++i) out[i] = f2i_x86(x[i]); }
+OR_EXPORT void or_dev_tex2d(const or_texture *table, const uint32_t *index, const float *u, const float *v, size_t n,
+                            float *rgb /* three planes of n */)
+{
+    for (size_t i = 0; i < n; ++i) {
+        v3 c = tex2d_bilinear(&table[index[i]], u[i], v[i], NULL);
+        rgb[i] = c.x; rgb[n + i] = c.y; rgb[2 * n + i] = c.z;
+    }
+}
+static void put_state(uint32_t *out, const xorwow_t *s)
+{
+    out[0] = s->d;
+    for (int k = 0; k < 5; ++k) out[1 + k] = s->v[k];
+}
+OR_EXPORT void or_dev_xorwow_init(const uint64_t *seed, size_t n, uint32_t *out)
+{
+    for (size_t i = 0; i < n; ++i) { xorwow_t s; or_xorwow_init(seed[i], &s); put_state(out + 6 * i, &s); }
+}
+OR_EXPORT void or_dev_xorwow_skip(const uint64_t *seed, const uint32_t *draws, size_t n, uint32_t *out)
+{
+    for (size_t i = 0; i < n; ++i) { xorwow_t s; or_xorwow_init(seed[i], &s); or_xorwow_skip(&s, draws[i]); put_state(out + 6 * i, &s); }
+}
+/* n outputs of xorwow_next, then n of curand_uniform, from one seed */
+OR_EXPORT void or_dev_xorwow_stream(uint64_t seed, size_t n, uint32_t *next, float *uniform)
+{
+    xorwow_t s;
+    or_xorwow_init(seed, &s);
+    for (size_t i = 0; i < n; ++i) next[i] = xorwow_next(&s);
+    for (size_t i = 0; i < n; ++i) uniform[i] = xorwow_uniform(&s);
+}
+
 OR_EXPORT uint32_t or_sizeof(int which)
 {
     switch (which) {

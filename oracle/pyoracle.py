@@ -121,6 +121,17 @@ def _bind(L: C.CDLL) -> C.CDLL:
         L.or_sample_log.argtypes = [P(Hittable), C.c_uint32, P(BVHNode), C.c_uint32, P(Camera), C.c_uint32, P(Texture),
                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(Xorwow), C.c_uint32,
                                     P(f), P(C.c_uint8)]
+        u32, u64, n = P(C.c_uint32), P(C.c_uint64), C.c_size_t
+        L.or_dev_sincos.argtypes = [P(f), n, P(f), P(f)]
+        for name in ("or_dev_acos", "or_dev_log", "or_dev_exp"):
+            getattr(L, name).argtypes = [P(f), n, P(f)]
+        for name in ("or_dev_atan2", "or_dev_pow"):
+            getattr(L, name).argtypes = [P(f), P(f), n, P(f)]
+        L.or_dev_f2i.argtypes = [P(f), n, P(C.c_int32)]
+        L.or_dev_tex2d.argtypes = [P(Texture), u32, P(f), P(f), n, P(f)]
+        L.or_dev_xorwow_init.argtypes = [u64, n, u32]
+        L.or_dev_xorwow_skip.argtypes = [u64, u32, n, u32]
+        L.or_dev_xorwow_stream.argtypes = [C.c_uint64, n, u32, P(f)]
         L.or_sizeof.restype = C.c_uint32
         L.or_sizeof.argtypes = [C.c_int]
     return L
@@ -513,3 +524,91 @@ def sample_log(scene: OracleScene, width: int, height: int, x: int, y: int, stat
         raise RuntimeError("oracle: BVH traversal stack overflow (reference UB)")
     return cols, pairs
 
+
+
+# ------------------------------------------------------------------------------------------------
+# the single operations over arrays (or_dev_*): float32 / uint32 arrays in, arrays out
+# ------------------------------------------------------------------------------------------------
+def _f32(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _u32ptr(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def dev_unary(name: str, x, fast: bool = False) -> np.ndarray:
+    """name in acos, log, exp: pm_acosf / pm_logf / pm_expf of every x."""
+    x = _f32(x)
+    out = np.empty_like(x)
+    getattr(lib(fast), "or_dev_" + name)(fptr(x), x.size, fptr(out))
+    return out
+
+
+def dev_binary(name: str, a, b, fast: bool = False) -> np.ndarray:
+    """name in atan2 (a = y, b = x), pow (a = x, b = y)."""
+    a, b = _f32(a), _f32(b)
+    assert a.shape == b.shape
+    out = np.empty_like(a)
+    getattr(lib(fast), "or_dev_" + name)(fptr(a), fptr(b), a.size, fptr(out))
+    return out
+
+
+def dev_sincos(x, fast: bool = False):
+    x = _f32(x)
+    s, c = np.empty_like(x), np.empty_like(x)
+    lib(fast).or_dev_sincos(fptr(x), x.size, fptr(s), fptr(c))
+    return s, c
+
+
+def dev_f2i(x, fast: bool = False) -> np.ndarray:
+    x = _f32(x)
+    out = np.empty(x.shape, dtype=np.int32)
+    lib(fast).or_dev_f2i(fptr(x), x.size, out.ctypes.data_as(C.POINTER(C.c_int32)))
+    return out
+
+
+def dev_tonemap(rgb, frames: int, fast: bool = False) -> np.ndarray:
+    """rgb (n, 3) accumulation values, one `frames` -> (n, 4) bytes."""
+    acc = np.zeros((len(rgb), 4), dtype=np.float32)
+    acc[:, :3] = rgb
+    out = np.zeros((len(rgb), 4), dtype=np.uint8)
+    lib(fast).or_tonemap(fptr(acc), len(rgb), frames, out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return out
+
+
+def dev_tex2d(textures: Sequence[np.ndarray], index, u, v, fast: bool = False) -> np.ndarray:
+    """textures: (H, W, 4) float32 arrays; index into them per input -> (3, n) r, g, b planes."""
+    texs = [np.ascontiguousarray(t, dtype=np.float32) for t in textures]
+    table = (Texture * len(texs))()
+    for i, t in enumerate(texs):
+        table[i].width, table[i].height, table[i].texels = t.shape[1], t.shape[0], fptr(t)
+    index = np.ascontiguousarray(index, dtype=np.uint32)
+    assert index.size == 0 or int(index.max()) < len(texs)
+    u, v = _f32(u), _f32(v)
+    out = np.empty((3, index.size), dtype=np.float32)
+    lib(fast).or_dev_tex2d(table, _u32ptr(index), fptr(u), fptr(v), index.size, fptr(out))
+    return out
+
+
+def dev_xorwow_init(seeds, fast: bool = False) -> np.ndarray:
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+    out = np.empty((seeds.size, 6), dtype=np.uint32)
+    lib(fast).or_dev_xorwow_init(seeds.ctypes.data_as(C.POINTER(C.c_uint64)), seeds.size, _u32ptr(out))
+    return out
+
+
+def dev_xorwow_skip(seeds, draws, fast: bool = False) -> np.ndarray:
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+    draws = np.ascontiguousarray(draws, dtype=np.uint32)
+    assert seeds.shape == draws.shape
+    out = np.empty((seeds.size, 6), dtype=np.uint32)
+    lib(fast).or_dev_xorwow_skip(seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _u32ptr(draws), seeds.size, _u32ptr(out))
+    return out
+
+
+def dev_xorwow_stream(seed: int, n: int, fast: bool = False):
+    """n outputs of xorwow_next (uint32), then n of curand_uniform (float32), from one seed."""
+    nxt, uni = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.float32)
+    lib(fast).or_dev_xorwow_stream(seed, n, _u32ptr(nxt), fptr(uni))
+    return nxt, uni

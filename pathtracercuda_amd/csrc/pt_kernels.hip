@@ -348,22 +348,7 @@ __global__ void __launch_bounds__(256) init_rng_kernel(uint32_t* rng, uint32_t w
     rng[5 * npix + li] = s.v4;
 }
 
-// tonemap (tonemap.cu:4-27) of one accumulation value over `frames` render() calls
-PT_DEV uchar4 tonemap_pixel(const float4 a, uint32_t frames)
-{
-    f3 c = divs(mk(a.x, a.y, a.z), (float)frames);
-    c = mul(mk(1.0f / (c.x + 1.0f), 1.0f / (c.y + 1.0f), 1.0f / (c.z + 1.0f)), c);
-    const float g = 1.0f / 2.2f;
-    const float ch[3] = {pow_(c.x, g), pow_(c.y, g), pow_(c.z, g)};
-    unsigned char q[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float f = ch[k] * 255.0f;
-        const int32_t v = (f != f) ? 0 : f2i_x86(f);
-        q[k] = (unsigned char)(v & 0xff);
-    }
-    return make_uchar4(q[0], q[1], q[2], 255);
-}
+#include "pt_dev_tonemap.h"
 
 __global__ void __launch_bounds__(256) tonemap_kernel(uchar4* out, const float4* accum, size_t npix, uint32_t frames)
 {
