@@ -235,6 +235,22 @@ public:
     float denoise(const DenoiseOptions& options);    // returns the sigma_color used
     float denoise() { return denoise(DenoiseOptions()); }
     bool denoised() const { return m_denoised; }     // the image calls return the denoised image
+    // Temporal reprojection (pt_temporal, pt_hip.h): per frame render(camera, spp, true), renderFeatures(camera),
+    // temporal().  The result of the previous temporal() is reprojected into this frame's camera, rejected
+    // where it is no longer the same surface, and this frame blended in.  Returns whether a previous history
+    // was used (none after reset, a scene load, a texture or another sky).  getTemporalHDRImageData returns the
+    // image (borrowed, rows x width x 4, w = the history length); getHDRImageData / getImageData and the
+    // accumulation are not changed.  Single device only.
+    struct TemporalOptions {
+        float alphaMin = PT_TEMPORAL_DEFAULT_ALPHA_MIN;
+        uint32_t maxHistory = PT_TEMPORAL_DEFAULT_MAX_HISTORY;
+        float sigmaPlane = PT_TEMPORAL_DEFAULT_SIGMA_PLANE;
+        float normalCosMin = PT_TEMPORAL_DEFAULT_NORMAL_COS_MIN;
+        uint32_t flags = PT_TEMPORAL_DEFAULT_FLAGS;
+    };
+    bool temporal(const TemporalOptions& options, bool reset = false);
+    bool temporal() { return temporal(TemporalOptions()); }
+    float* getTemporalHDRImageData();
     float getTiming() const;
     uint32_t loadTexture(const char* path);
     void setSkyboxTextureHandle(uint32_t handle);
@@ -269,6 +285,7 @@ private:
     bool m_adaptive = false;
     bool m_denoised = false;
     std::vector<float> m_featureBuffer;
+    std::vector<float> m_temporalBuffer;
     BVH m_bvh;
     void allocHostBuffers();
     void check(int rc, const char* what) const;

@@ -380,7 +380,7 @@ PT_API int pt_read_group_log_counts(pt_context *ctx, uint32_t *dst, size_t count
  * launch's guesses use (float): draw pairs per sample, odd-length fraction, variance. */
 PT_API int pt_read_group_fold(pt_context *ctx, uint32_t word, uint32_t *dst);
 /* The message of the context's last failed call.  With ctx = NULL: the message of the calling thread's
- * last failed context-free call (pt_denoise_image). */
+ * last failed context-free call (pt_denoise_image, pt_temporal_image). */
 PT_API const char *pt_last_error(const pt_context *ctx);
 
 /* ---- First-hit feature buffers ------------------------------------------------------------------
@@ -480,6 +480,96 @@ PT_API int pt_tonemap_denoised(pt_context *ctx, uint8_t *dst);
  * pt_last_error(NULL). */
 PT_API int pt_denoise_image(int device, uint32_t width, uint32_t height, const float *color, const float *plane0,
                             const float *plane1, const float *plane2, const pt_denoise_params *params, float *out);
+
+/* ---- Temporal reprojection ------------------------------------------------------------------------
+ * One step per frame: last frame's result is reprojected into this frame's camera through the feature
+ * planes, what is no longer the same surface is rejected, and the new frame is blended in.  All float32,
+ * no contraction, + - x /, floor, compares and selects only, in exactly these operations
+ * (tests/temporal_model.py restates them).  Every dot product a . b is (a.x*b.x + a.y*b.y) + a.z*b.z;
+ * "finite" means x - x == 0.
+ *
+ * History, three float4 per pixel:  h0 = (I.rgb, n): the accumulated (demodulated) colour and the history
+ * length n, a float holding an integer, 0 = no history here;  h1 = (N, id bits);  h2 = (P, t).
+ * Inputs of a step: the colour C; the planes 0..2 (A, id | N, t | P, flags) and their camera `cur`; the
+ * previous history with its camera `prev`, or none.  W, H = the image's width and height as floats.
+ *
+ * Per pixel p = (x, y), y the global row:
+ *     ok_p  = HIT && every component x of C, N, P is finite        (emissive surfaces are included)
+ *     D     = DEMODULATE ? (A > 1/64 ? A : 1/64) per channel : 1;    I_cur = C / D
+ *     h1 = (N_p, id_p), h2 = (P_p, t_p) in every case
+ *     !ok_p:  image = (C.rgb, 0), h0 = (C.rgb, 0), and nothing else is done for the pixel
+ *     project(cam, P):  e = P - cam.origin;  z = -(e . cam.backward);  hh = cam.tan_half_fovy;
+ *                       hw = cam.aspect_ratio * hh;
+ *                       su = ((e . cam.right / z) / hw) * 0.5 + 0.5;  sv = ((e . cam.up / z) / hh) * 0.5 + 0.5
+ *     (su0, sv0, z0) = project(cur, P_p);  (su1, sv1, z1) = project(prev, P_p)
+ *     fx = (float)x + (su1 - su0) * W;  fy = (float)y + (sv1 - sv0) * H
+ *       (the planes hold the hit of a jittered ray: subtracting the current projection removes the jitter;
+ *       with prev == cur both projections are the same operations on the same words: fx = x, fy = y)
+ *     reproj = z0 > 0 && z1 > 0 && fx > -1 && fx < W && fy > -1 && fy < H        (a NaN fails it; floats
+ *       are converted to integers only behind it)
+ *     x0 = floor(fx), ax = fx - x0;  y0 = floor(fy), ay = fy - y0
+ *     sumW = 0, sumI = (0, 0, 0), nh = (float)max_history
+ *     taps (i, j) = (0,0), (1,0), (0,1), (1,1) at q = (x0 + i, y0 + j):  w = (i ? ax : 1 - ax) * (j ? ay : 1 - ay)
+ *       a tap is skipped (by a select, never by a zero weight; its index is clamped into the image before
+ *       the load) when  !(w > 0),  or q is outside the image,  or n_q < 1,  or a component of I_q is not
+ *       finite,  or SAME_PRIMITIVE is set and id_q != id_p,  or N_p . N_q < normal_cos_min,  or, with
+ *       g = N_p . (P_q - P_p) and m = sigma_plane * t_p,  !(g*g <= m*m);  otherwise
+ *         sumW = sumW + w;  sumI = sumI + w * I_q (per channel);  nh = n_q < nh ? n_q : nh
+ *     have = there is a previous history && reproj && sumW >= 1/64
+ *     have:   Hc = sumI / sumW;  n = nh + 1;  n = n < (float)max_history ? n : (float)max_history;
+ *             a = 1 / n;  a = a > alpha_min ? a : alpha_min;  I = Hc + a * (I_cur - Hc)
+ *     else:   I = I_cur, n = 1
+ *     image = (I * D, n);  h0 = (I, n)
+ * With prev == cur, flags 0 and alpha_min 0 every hit pixel takes exactly one tap of weight 1 (itself), so
+ * after K steps h0 is the running mean  m = m + (1/k) * (C_k - m)  word for word, and n = K.
+ * Accepted: alpha_min 0..1, max_history 1..65535, sigma_plane >= 1e-6 and finite, normal_cos_min -1..1,
+ * flags within the two bits; anything else (a NaN included) is PT_ERR_ARG and the message names the field. */
+#define PT_TEMPORAL_DEMODULATE 1u
+#define PT_TEMPORAL_SAME_PRIMITIVE 2u
+/* Defaults of the layers above (C++ Pathtracer::temporal, Python), chosen by the sweep of
+ * tools/temporal_probe.py (profiles/temporal_probe.json). */
+#define PT_TEMPORAL_DEFAULT_ALPHA_MIN 0.02f
+#define PT_TEMPORAL_DEFAULT_MAX_HISTORY 64
+#define PT_TEMPORAL_DEFAULT_SIGMA_PLANE 0.3f
+#define PT_TEMPORAL_DEFAULT_NORMAL_COS_MIN 0.0f
+#define PT_TEMPORAL_DEFAULT_FLAGS 1u
+typedef struct pt_temporal_params {
+    float alpha_min;         /* the least weight of the new frame */
+    uint32_t max_history;    /* n is capped here */
+    float sigma_plane;       /* relative to the hit distance */
+    float normal_cos_min;
+    uint32_t flags;
+} pt_temporal_params;
+
+/* One step on the context.  C is formed as pt_denoise forms it (accumulation * (1 / max(frames, 1)), or
+ * accumulation / n per pixel while pt_holds_adaptive); the planes and `cur` are those of the last
+ * pt_render_features; the previous history is the one the last pt_temporal left, used when one is held and
+ * reset == 0 (history_used, optional, receives 1 then, else 0).  The context keeps two history sets: a step
+ * reads one and writes the other.  A history is held from the end of a pt_temporal until the next one
+ * begins, a scene or texture change, or a sky change to another handle; a camera change, a render and an
+ * RNG write end nothing.  The pass reads and writes nothing of the render state, as the denoiser.
+ * PT_ERR_STATE, naming the reason, without current feature planes; PT_ERR_ARG, naming the reason, on a
+ * context that does not hold the whole frame (gather the frame and use pt_temporal_image). */
+PT_API int pt_temporal(pt_context *ctx, uint32_t frames, const pt_temporal_params *params, int reset,
+                       int *history_used);
+/* The last pt_temporal's image (rows x width float4, w = n), its tonemap (pt_tonemap_denoised's
+ * arithmetic; RGBA8) and its kernel's hipEvent time in ms (one float).  PT_ERR_STATE when there is none. */
+PT_API int pt_read_temporal(pt_context *ctx, float *dst);
+PT_API int pt_tonemap_temporal(pt_context *ctx, uint8_t *dst);
+PT_API int pt_read_temporal_timing(pt_context *ctx, float *dst);
+/* pt_denoise's filter with the temporal image as its colour and the planes that image was made from as its
+ * guide; the result goes where pt_denoise's goes (pt_read_denoised, pt_tonemap_denoised).  PT_ERR_STATE
+ * when there is no temporal image or pt_render_features has run since it was made. */
+PT_API int pt_denoise_temporal(pt_context *ctx, const pt_denoise_params *params);
+/* The same step on host arrays, without a context: color, plane0..2, hist0..2, out_image and out_hist0..2
+ * are height x width float4 (color's w is ignored); hist0 = NULL means no previous history (hist1, hist2
+ * and prev_cam are not read then).  For a frame gathered from several devices, and for tests.  Errors:
+ * pt_last_error(NULL). */
+PT_API int pt_temporal_image(int device, uint32_t width, uint32_t height, const float *color, const float *plane0,
+                             const float *plane1, const float *plane2, const pt_camera *cur_cam, const float *hist0,
+                             const float *hist1, const float *hist2, const pt_camera *prev_cam,
+                             const pt_temporal_params *params, float *out_image, float *out_hist0, float *out_hist1,
+                             float *out_hist2);
 
 /* ---- Multi-device group (one process, one context per GPU, RCCL over xGMI) -------------------
  * Replaces the reference's hard-coded single device (Pathtracer.cpp:40: cudaSetDevice(0)) behind

@@ -90,6 +90,13 @@ PT_API int pth_renderer_features(pth_renderer *r, const pt_camera *camera);
 PT_API const float *pth_renderer_feature_plane(pth_renderer *r, uint32_t plane);
 PT_API int pth_renderer_denoise(pth_renderer *r, const pt_denoise_params *params, int auto_sigma, float *sigma_used);
 PT_API int pth_renderer_denoised(const pth_renderer *r);
+/* Pathtracer::temporal / getTemporalHDRImageData (pt_temporal, pt_hip.h; single device): one step of temporal
+ * reprojection with the planes of the last pth_renderer_features; history_used (optional) receives whether a
+ * previous history was used.  pth_renderer_temporal_hdr: the image, a borrowed pointer (rows x width float4,
+ * w = the history length) valid until the next call, null on error.  pth_renderer_hdr / pth_renderer_image
+ * are not changed by either. */
+PT_API int pth_renderer_temporal(pth_renderer *r, const pt_temporal_params *params, int reset, int *history_used);
+PT_API const float *pth_renderer_temporal_hdr(pth_renderer *r);
 PT_API float pth_renderer_timing(const pth_renderer *r);
 PT_API uint32_t pth_renderer_frames(const pth_renderer *r);
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer *r);

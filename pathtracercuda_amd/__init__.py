@@ -26,7 +26,8 @@ from ._native import PathtracerError, PtBvhNode, PtCamera, PtHittable, PtRenderS
 
 __all__ = ["Pathtracer", "Scene", "make_camera", "camera_rotate", "camera_translate", "radians", "device_count", "PathtracerError", "PtCamera",
            "PtBvhNode", "PtHittable", "write_png", "write_hdr", "HITTABLE_TYPES", "MATERIAL_TYPES", "denoise_image",
-           "denoise_params", "auto_sigma_color", "denoise_keep_mask", "DENOISE_DEFAULTS", "DENOISE_SIGMA_FACTOR"]
+           "denoise_params", "auto_sigma_color", "denoise_keep_mask", "DENOISE_DEFAULTS", "DENOISE_SIGMA_FACTOR",
+           "temporal_params", "temporal_image", "TEMPORAL_DEFAULTS"]
 
 HITTABLE_TYPES = ["SPHERE", "CYLINDER", "DISK", "CONE", "PARABOLOID", "QUAD", "CUBE"]   # Hittable.h:9-12
 MATERIAL_TYPES = ["LAMBERT", "GGX", "LAMBERT_GGX"]                                     # Material.h:9-12
@@ -163,6 +164,68 @@ def denoise_image(color, plane0, plane1, plane2, iterations: int = 5, sigma_colo
                                   out.ctypes.data_as(fp))
     N.check_ctx(rc, None)
     return out
+
+
+# Defaults of the temporal pass, chosen by the sweep of tools/temporal_probe.py (profiles/temporal_probe.json;
+# argued in DESIGN.md §5.9).
+TEMPORAL_DEFAULTS = {"alpha_min": 0.02, "max_history": 64, "sigma_plane": 0.3, "normal_cos_min": 0.0,
+                     "demodulate": True, "same_primitive": False}
+
+
+def temporal_params(alpha_min: Optional[float] = None, max_history: Optional[int] = None,
+                    sigma_plane: Optional[float] = None, normal_cos_min: Optional[float] = None,
+                    demodulate: Optional[bool] = None, same_primitive: Optional[bool] = None) -> "N.PtTemporalParams":
+    """pt_temporal_params from keyword arguments, refused here (PT_ERR_ARG naming the field) before any
+    device call when a value is outside the accepted range of include/pt_hip.h."""
+    d = TEMPORAL_DEFAULTS
+    alpha_min = d["alpha_min"] if alpha_min is None else alpha_min
+    max_history = d["max_history"] if max_history is None else max_history
+    sigma_plane = d["sigma_plane"] if sigma_plane is None else sigma_plane
+    normal_cos_min = d["normal_cos_min"] if normal_cos_min is None else normal_cos_min
+    demodulate = d["demodulate"] if demodulate is None else demodulate
+    same_primitive = d["same_primitive"] if same_primitive is None else same_primitive
+    am, sp, nc = np.float32(alpha_min), np.float32(sigma_plane), np.float32(normal_cos_min)
+    if not 0 <= am <= 1:
+        raise _refuse(f"temporal: alpha_min must be 0..1, not {alpha_min!r}")
+    if isinstance(max_history, float) and not np.isfinite(max_history):
+        raise _refuse(f"temporal: max_history must be 1..65535, not {max_history!r}")
+    if int(max_history) != max_history or not 1 <= int(max_history) <= 65535:
+        raise _refuse(f"temporal: max_history must be 1..65535, not {max_history!r}")
+    if not (sp >= np.float32(1e-6) and np.isfinite(sp)):
+        raise _refuse(f"temporal: sigma_plane must be >= 1e-6 and finite, not {sigma_plane!r}")
+    if not -1 <= nc <= 1:
+        raise _refuse(f"temporal: normal_cos_min must be -1..1, not {normal_cos_min!r}")
+    flags = (N.PT_TEMPORAL_DEMODULATE if demodulate else 0) | (N.PT_TEMPORAL_SAME_PRIMITIVE if same_primitive else 0)
+    return N.PtTemporalParams(float(am), int(max_history), float(sp), float(nc), flags)
+
+
+def temporal_image(color, plane0, plane1, plane2, cur_camera: PtCamera, history=None, prev_camera: Optional[PtCamera] = None,
+                   alpha_min: Optional[float] = None, max_history: Optional[int] = None, sigma_plane: Optional[float] = None,
+                   normal_cos_min: Optional[float] = None, demodulate: Optional[bool] = None,
+                   same_primitive: Optional[bool] = None, device: int = 0):
+    """pt_temporal_image: one step of the temporal rule of include/pt_hip.h on host arrays (height x width x 4
+    float32), without a Pathtracer.  `history` = the (h0, h1, h2) an earlier step returned, with that step's
+    camera as `prev_camera`, or None.  Returns (image, h0, h1, h2)."""
+    params = temporal_params(alpha_min, max_history, sigma_plane, normal_cos_min, demodulate, same_primitive)
+    c = _image4("color", color)
+    arrays = [c] + [_image4(f"plane{k}", p, c.shape) for k, p in enumerate((plane0, plane1, plane2))]
+    fp = C.POINTER(C.c_float)
+    null = C.cast(None, fp)
+    if history is not None:
+        if prev_camera is None:
+            raise _refuse("temporal_image: history is given without prev_camera")
+        hist = [_image4(f"history[{k}]", h, c.shape) for k, h in enumerate(history)]
+        if len(hist) != 3:
+            raise _refuse("temporal_image: history must be (h0, h1, h2)")
+        hp = [h.ctypes.data_as(fp) for h in hist]
+    else:
+        hp = [null, null, null]
+    outs = [np.zeros_like(c) for _ in range(4)]
+    rc = N.hip().pt_temporal_image(int(device), c.shape[1], c.shape[0], *[a.ctypes.data_as(fp) for a in arrays],
+                                   C.byref(cur_camera), *hp, C.byref(prev_camera) if prev_camera is not None else None,
+                                   C.byref(params), *[o.ctypes.data_as(fp) for o in outs])
+    N.check_ctx(rc, None)
+    return tuple(outs)
 
 
 class Scene:
@@ -379,17 +442,30 @@ class Pathtracer:
 
     def denoise(self, iterations: int = 5, sigma_color: Optional[float] = None, sigma_plane: Optional[float] = None,
                 normal_power_log2: Optional[int] = None, demodulate: Optional[bool] = None,
-                same_primitive: Optional[bool] = None, staging: int = 0, frames: Optional[int] = None) -> np.ndarray:
+                same_primitive: Optional[bool] = None, staging: int = 0, frames: Optional[int] = None,
+                source: str = "accumulation") -> np.ndarray:
         """Filter the image with the edge-avoiding a-trous denoiser (include/pt_hip.h), guided by the
         planes of the last features(camera) call; returns rows x width x 4 float32 in
         get_hdr_image_data()'s units and leaves the accumulation as it is.  sigma_color=None: a factor times
         the median luminance of the kept pixels (auto_sigma_color).  `frames`: the divisor of the
         accumulation (default: the frame counter; an adaptive render divides every pixel by its own count).
+        source="temporal": the image of the last temporal() is filtered instead (pt_denoise_temporal), guided
+        by the planes it was made from; the automatic sigma is then of that image.
         Arguments out of range raise before any device call."""
         self._single("denoise")
+        if source not in ("accumulation", "temporal"):
+            raise _refuse(f"denoise: source must be 'accumulation' or 'temporal', not {source!r}")
         demod = DENOISE_DEFAULTS["demodulate"] if demodulate is None else demodulate
         params = denoise_params(iterations, 1.0 if sigma_color is None else sigma_color, sigma_plane, normal_power_log2,
                                 demod, same_primitive, staging)
+        if source == "temporal":
+            if sigma_color is None:
+                planes = getattr(self, "_planes", None)
+                if planes is None:
+                    raise PathtracerError(N.PT_ERR_STATE, "denoise: no feature planes (call features(camera) first)")
+                params.sigma_color = auto_sigma_color(self.temporal_image(), *planes, demodulate=demod)
+            N.check_ctx(N.hip().pt_denoise_temporal(self._ctx, C.byref(params)), self._ctx)
+            return self.denoised()
         f = self.frames if frames is None else int(frames)
         if sigma_color is None:
             planes = getattr(self, "_planes", None)
@@ -427,6 +503,51 @@ class Pathtracer:
         N.check_ctx(N.hip().pt_read_features_timing(self._ctx, C.byref(fm)), self._ctx)
         return {"features": float(fm.value), "prepare": float(ms[0]), "iterations": [float(x) for x in ms[1:9]],
                 "finish": float(ms[9])}
+
+    # --- temporal reprojection (pt_temporal; pt_hip.h) ---------------------------------------------
+    def temporal(self, alpha_min: Optional[float] = None, max_history: Optional[int] = None,
+                 sigma_plane: Optional[float] = None, normal_cos_min: Optional[float] = None, demodulate: Optional[bool] = None,
+                 same_primitive: Optional[bool] = None, reset: bool = False, frames: Optional[int] = None) -> np.ndarray:
+        """One step of temporal accumulation (include/pt_hip.h): the result of the previous temporal() is
+        reprojected into the camera of the last features(camera) through its planes, rejected where it is no
+        longer the same surface, and the current image blended in.  Call order per frame:
+        render(cam, spp, True), features(cam), temporal().  Returns the image, rows x width x 4 float32 in
+        get_hdr_image_data()'s units with w = the history length; `history_used` tells whether a previous
+        history was held (none after reset=True, a scene load, a texture or another sky).  Touches nothing of
+        the render state.  Arguments out of range raise before any device call."""
+        self._single("temporal")
+        params = temporal_params(alpha_min, max_history, sigma_plane, normal_cos_min, demodulate, same_primitive)
+        f = self.frames if frames is None else int(frames)
+        used = C.c_int(0)
+        N.check_ctx(N.hip().pt_temporal(self._ctx, f, C.byref(params), int(bool(reset)), C.byref(used)), self._ctx)
+        self.history_used = bool(used.value)
+        return self.temporal_image()
+
+    def temporal_image(self) -> np.ndarray:
+        """The last temporal()'s image again (pt_read_temporal)."""
+        self._single("temporal_image")
+        out = np.zeros((self.rows, self.width, 4), dtype=np.float32)
+        N.check_ctx(N.hip().pt_read_temporal(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float))), self._ctx)
+        return out
+
+    def history_lengths(self) -> np.ndarray:
+        """The history length n of every pixel after the last temporal() (rows x width float32; 0 = not a
+        finite hit, 1 = this frame alone)."""
+        return self.temporal_image()[..., 3].copy()
+
+    def tonemap_temporal(self) -> np.ndarray:
+        """The last temporal()'s image through the tonemap (RGBA8, rows x width)."""
+        self._single("tonemap_temporal")
+        out = np.zeros((self.rows, self.width, 4), dtype=np.uint8)
+        N.check_ctx(N.hip().pt_tonemap_temporal(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint8))), self._ctx)
+        return out
+
+    def temporal_timing(self) -> float:
+        """Kernel time of the last temporal() in ms (hipEvents)."""
+        self._single("temporal_timing")
+        ms = C.c_float(0.0)
+        N.check_ctx(N.hip().pt_read_temporal_timing(self._ctx, C.byref(ms)), self._ctx)
+        return float(ms.value)
 
     def get_timing(self) -> float:
         return float(N.host().pth_renderer_timing(self._r))

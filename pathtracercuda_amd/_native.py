@@ -67,7 +67,14 @@ class PtDenoiseParams(C.Structure):
                 ("normal_power_log2", C.c_uint32), ("flags", C.c_uint32), ("staging", C.c_uint32)]
 
 
+class PtTemporalParams(C.Structure):
+    """pt_temporal_params (pt_hip.h, temporal reprojection)."""
+    _fields_ = [("alpha_min", C.c_float), ("max_history", C.c_uint32), ("sigma_plane", C.c_float),
+                ("normal_cos_min", C.c_float), ("flags", C.c_uint32)]
+
+
 PT_FEATURE_HIT, PT_FEATURE_EMISSIVE = 1, 2
+PT_TEMPORAL_DEMODULATE, PT_TEMPORAL_SAME_PRIMITIVE = 1, 2
 PT_DENOISE_DEMODULATE, PT_DENOISE_SAME_PRIMITIVE = 1, 2
 PT_DENOISE_TILE_W, PT_DENOISE_TILE_H = 32, 8
 
@@ -133,6 +140,14 @@ _HIP_SYMBOLS = {
     "pt_tonemap_denoised": (C.c_int, [C.c_void_p, P(C.c_uint8)]),
     "pt_denoise_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, P(C.c_float), P(C.c_float), P(C.c_float),
                                    P(C.c_float), P(PtDenoiseParams), P(C.c_float)]),
+    "pt_temporal": (C.c_int, [C.c_void_p, C.c_uint32, P(PtTemporalParams), C.c_int, P(C.c_int)]),
+    "pt_read_temporal": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_tonemap_temporal": (C.c_int, [C.c_void_p, P(C.c_uint8)]),
+    "pt_read_temporal_timing": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_denoise_temporal": (C.c_int, [C.c_void_p, P(PtDenoiseParams)]),
+    "pt_temporal_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                    P(PtCamera), P(C.c_float), P(C.c_float), P(C.c_float), P(PtCamera), P(PtTemporalParams),
+                                    P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float)]),
     "pt_group_create": (C.c_int, [C.c_int, P(C.c_int), C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_void_p)]),
     "pt_group_destroy": (None, [C.c_void_p]),
     "pt_group_size": (C.c_int, [C.c_void_p]),
@@ -180,6 +195,8 @@ _HOST_SYMBOLS = {
     "pth_renderer_feature_plane": (P(C.c_float), [C.c_void_p, C.c_uint32]),
     "pth_renderer_denoise": (C.c_int, [C.c_void_p, P(PtDenoiseParams), C.c_int, P(C.c_float)]),
     "pth_renderer_denoised": (C.c_int, [C.c_void_p]),
+    "pth_renderer_temporal": (C.c_int, [C.c_void_p, P(PtTemporalParams), C.c_int, P(C.c_int)]),
+    "pth_renderer_temporal_hdr": (P(C.c_float), [C.c_void_p]),
     "pth_renderer_timing": (C.c_float, [C.c_void_p]),
     "pth_renderer_frames": (C.c_uint32, [C.c_void_p]),
     "pth_renderer_local_rows": (C.c_uint32, [C.c_void_p]),

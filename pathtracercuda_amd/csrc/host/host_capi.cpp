@@ -338,6 +338,30 @@ PT_API int pth_renderer_denoise(pth_renderer* r, const pt_denoise_params* params
 
 PT_API int pth_renderer_denoised(const pth_renderer* r) { return r && r->pt->denoised() ? 1 : 0; }
 
+PT_API int pth_renderer_temporal(pth_renderer* r, const pt_temporal_params* params, int reset, int* history_used)
+{
+    if (!r || !params) return setError(PT_ERR_ARG, "invalid argument");
+    PTH_GUARD_BEGIN
+    Pathtracer::TemporalOptions o;
+    o.alphaMin = params->alpha_min;
+    o.maxHistory = params->max_history;
+    o.sigmaPlane = params->sigma_plane;
+    o.normalCosMin = params->normal_cos_min;
+    o.flags = params->flags;
+    const bool used = r->pt->temporal(o, reset != 0);
+    if (history_used) *history_used = used ? 1 : 0;
+    return PT_OK;
+    PTH_GUARD_END
+}
+
+PT_API const float* pth_renderer_temporal_hdr(pth_renderer* r)
+{
+    if (!r) return nullptr;
+    ptamd::g_throwOnError = true;
+    try { return r->pt->getTemporalHDRImageData(); } catch (const std::exception& e) { setError(PT_ERR_STATE, e.what()); }
+    return nullptr;
+}
+
 PT_API float pth_renderer_timing(const pth_renderer* r) { return r ? r->pt->getTiming() : 0.0f; }
 PT_API uint32_t pth_renderer_frames(const pth_renderer* r) { return r ? r->pt->accumulatedFrames() : 0; }
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer* r) { return r ? r->pt->localRows() : 0; }

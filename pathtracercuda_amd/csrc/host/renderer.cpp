@@ -211,6 +211,23 @@ float Pathtracer::denoise(const DenoiseOptions& o)
     return p.sigma_color;
 }
 
+bool Pathtracer::temporal(const TemporalOptions& o, bool reset)
+{
+    if (m_group) check(PT_ERR_STATE, "temporal: not available on a device group");
+    const pt_temporal_params p = {o.alphaMin, o.maxHistory, o.sigmaPlane, o.normalCosMin, o.flags};
+    int used = 0;
+    check(pt_temporal(m_ctx, m_accumulatedFrames, &p, reset ? 1 : 0, &used), "pt_temporal");
+    return used != 0;
+}
+
+float* Pathtracer::getTemporalHDRImageData()
+{
+    if (m_group) check(PT_ERR_STATE, "getTemporalHDRImageData: not available on a device group");
+    m_temporalBuffer.resize((size_t)localRows() * m_width * 4);
+    check(pt_read_temporal(m_ctx, m_temporalBuffer.data()), "pt_read_temporal");
+    return m_temporalBuffer.data();
+}
+
 float Pathtracer::getTiming() const { return m_timing; }
 
 uint32_t Pathtracer::loadTexture(const char* path)

@@ -1,6 +1,6 @@
 // pt_ctx_state.h -- what a context carries from one call to the next, and every rule that moves it:
-// no HIP call, no context, plain values.  The C ABI functions (pt_kernels.hip, pt_denoise.h) raise the
-// events below and ask the predicates; they assign none of these fields themselves.
+// no HIP call, no context, plain values.  The C ABI functions (pt_kernels.hip, pt_denoise.h, pt_temporal.h)
+// raise the events below and ask the predicates; they assign none of these fields themselves.
 // tools/ctx_state_check.cpp and tests/test_ctx_state.py run the same functions on the CPU.
 //
 // The facts, what each means and which events end it (DESIGN.md 5.8 has the host layer's flags):
@@ -24,6 +24,16 @@
 //                   is done, ended by its beginning and by a scene or texture change.
 //   dnValid         a denoised image is held: ended when a denoise has passed its checks, set when it is
 //                   done, so only a denoise that fails midway (a HIP error) leaves none.
+//   tpValid         a temporal image is held (pt_read_temporal): ended when a temporal pass has passed its
+//                   checks, set when it is done.
+//   histValid       a history is held, which the next temporal pass may reproject: set when a temporal pass
+//                   is done, ended by its beginning, by a scene or texture change and by a sky change to
+//                   another handle (the colours it holds are of that scene and sky).  A camera change, a
+//                   render and an RNG write end nothing: moving the camera is what the pass is for, and new
+//                   samples of the same scene are what it blends in.  Implies tpValid.
+//   tpOfPlanes      the temporal image was made from the planes the context holds now (pt_denoise_temporal's
+//                   guide): set when a temporal pass is done, ended by its beginning and by the beginning
+//                   of a features call.  Implies tpValid.
 //   epoch           counts the launches that wrote the accumulation (a device group's gather cache
 //                   key, pt_group.h).  Never decreases.
 // A call refused for its arguments or for the state raises no event (but for a render whose plan is a
@@ -45,6 +55,7 @@ struct CtxState {
     uint32_t aheadMisses = 0;
     bool adMomValid = false, adCountsValid = false;
     bool featValid = false, dnValid = false;
+    bool tpValid = false, histValid = false, tpOfPlanes = false;
     uint64_t epoch = 0;
 };
 
@@ -55,6 +66,7 @@ inline void scene_or_texture_changed(CtxState& s)
     s.order.stale = true;
     s.adMomValid = false;
     s.featValid = false;
+    s.histValid = false;
     ++s.stateEpoch;
 }
 
@@ -65,6 +77,7 @@ inline void sky_set(CtxState& s, uint32_t held, uint32_t handle)
     if (held == handle) return;
     ++s.stateEpoch;
     s.adMomValid = false;
+    s.histValid = false;
 }
 
 // pt_write_rng: a stash and the moments continue the old streams
@@ -143,15 +156,34 @@ inline void adaptive_done(CtxState& s)
     s.adCountsValid = true;
 }
 
-inline void features_begin(CtxState& s) { s.featValid = false; }
+inline void features_begin(CtxState& s)
+{
+    s.featValid = false;
+    s.tpOfPlanes = false;
+}
 inline void features_done(CtxState& s) { s.featValid = true; }
 inline void denoise_begins(CtxState& s) { s.dnValid = false; }
 inline void denoise_done(CtxState& s) { s.dnValid = true; }
+inline void temporal_begins(CtxState& s)
+{
+    s.tpValid = false;
+    s.histValid = false;
+    s.tpOfPlanes = false;
+}
+inline void temporal_done(CtxState& s)
+{
+    s.tpValid = true;
+    s.histValid = true;
+    s.tpOfPlanes = true;
+}
 
 // ---- predicates -----------------------------------------------------------------------------------
 inline bool counts_describe_buffer(const CtxState& s) { return s.adCountsValid; }
 inline bool moments_continue(const CtxState& s) { return s.adMomValid; }
 inline bool planes_current(const CtxState& s) { return s.featValid; }
 inline bool holds_denoised(const CtxState& s) { return s.dnValid; }
+inline bool holds_temporal(const CtxState& s) { return s.tpValid; }
+inline bool history_held(const CtxState& s) { return s.histValid; }
+inline bool temporal_of_planes(const CtxState& s) { return s.tpOfPlanes; }
 
 } // namespace pt

@@ -81,6 +81,39 @@ static hipError_t denoise_run(hipStream_t stream, const pt_denoise_params& p, ui
     return hipSuccess;
 }
 
+// The filter on a whole-frame context whose arguments and state have been checked, guided by its feature
+// planes: of `color` (device memory of the context, pt_denoise_temporal) or, when that is null, of the
+// accumulation over `frames` or the per-pixel counts (pt_denoise).  The result goes to the context's
+// denoised image, the kernel times to dnMs.
+static int denoise_context(pt_context* ctx, const pt_denoise_params& p, const float4* color, uint32_t frames)
+{
+    PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const size_t npix = (size_t)ctx->rows * ctx->width;
+    denoise_begins(ctx->st);
+    if (!ctx->dnBuf) {
+        PT_HIP_CHECK(ctx, hipMalloc(&ctx->dnBuf, 6 * npix * sizeof(float4)));   // colour, g0, g1, ping, pong, out
+        for (auto& e : ctx->dnEv) PT_HIP_CHECK(ctx, hipEventCreate(&e));
+    }
+    if (!color) {
+        const float inv = 1.0f / fmaxf((float)frames, 1.0f);
+        dn_color_kernel<<<(unsigned)((npix + 255) / 256), 256, 0, ctx->stream>>>(
+            ctx->dnBuf, ctx->accum, counts_describe_buffer(ctx->st) ? ctx->adMom + 2 * npix : nullptr, npix, inv);
+        PT_HIP_CHECK(ctx, hipGetLastError());
+        color = ctx->dnBuf;
+    }
+    PT_HIP_CHECK(ctx, denoise_run(ctx->stream, p, ctx->width, ctx->height, color, ctx->feat, ctx->dnBuf + npix,
+                                  ctx->dnBuf + 2 * npix, ctx->dnBuf + 3 * npix, ctx->dnBuf + 4 * npix,
+                                  ctx->dnBuf + 5 * npix, ctx->dnEv));
+    PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    for (float& m : ctx->dnMs) m = 0.0f;
+    PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[0], ctx->dnEv[0], ctx->dnEv[1]));
+    for (uint32_t i = 0; i < p.iterations; ++i)
+        PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[1 + i], ctx->dnEv[1 + i], ctx->dnEv[2 + i]));
+    PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[9], ctx->dnEv[1 + p.iterations], ctx->dnEv[11]));
+    denoise_done(ctx->st);
+    return PT_OK;
+}
+
 extern "C" {
 
 PT_API int pt_render_features(pt_context* ctx, const pt_camera* camera)
@@ -90,6 +123,7 @@ PT_API int pt_render_features(pt_context* ctx, const pt_camera* camera)
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->rows * ctx->width;
     features_begin(ctx->st);
+    ctx->featCam = *camera;
     if (!ctx->feat) PT_HIP_CHECK(ctx, hipMalloc(&ctx->feat, 3 * std::max(npix, (size_t)1) * sizeof(float4)));
     ctx->featMs = 0.0f;
     if (npix) {
@@ -156,29 +190,7 @@ PT_API int pt_denoise(pt_context* ctx, uint32_t frames, const pt_denoise_params*
                                      "(gather the frame and use pt_denoise_image)");
     if (!planes_current(ctx->st))
         return fail(ctx, PT_ERR_STATE, "pt_denoise: no feature planes (no pt_render_features since the scene or a texture was set)");
-    PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const size_t npix = (size_t)ctx->rows * ctx->width;
-    denoise_begins(ctx->st);
-    if (!ctx->dnBuf) {
-        PT_HIP_CHECK(ctx, hipMalloc(&ctx->dnBuf, 6 * npix * sizeof(float4)));   // colour, g0, g1, ping, pong, out
-        for (auto& e : ctx->dnEv) PT_HIP_CHECK(ctx, hipEventCreate(&e));
-    }
-    float4* color = ctx->dnBuf;
-    const float inv = 1.0f / fmaxf((float)frames, 1.0f);
-    dn_color_kernel<<<(unsigned)((npix + 255) / 256), 256, 0, ctx->stream>>>(
-        color, ctx->accum, counts_describe_buffer(ctx->st) ? ctx->adMom + 2 * npix : nullptr, npix, inv);
-    PT_HIP_CHECK(ctx, hipGetLastError());
-    PT_HIP_CHECK(ctx, denoise_run(ctx->stream, *params, ctx->width, ctx->height, color, ctx->feat, ctx->dnBuf + npix,
-                                  ctx->dnBuf + 2 * npix, ctx->dnBuf + 3 * npix, ctx->dnBuf + 4 * npix,
-                                  ctx->dnBuf + 5 * npix, ctx->dnEv));
-    PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    for (float& m : ctx->dnMs) m = 0.0f;
-    PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[0], ctx->dnEv[0], ctx->dnEv[1]));
-    for (uint32_t i = 0; i < params->iterations; ++i)
-        PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[1 + i], ctx->dnEv[1 + i], ctx->dnEv[2 + i]));
-    PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[9], ctx->dnEv[1 + params->iterations], ctx->dnEv[11]));
-    denoise_done(ctx->st);
-    return PT_OK;
+    return denoise_context(ctx, *params, nullptr, frames);
 }
 
 PT_API int pt_read_denoise_timing(pt_context* ctx, float* dst)

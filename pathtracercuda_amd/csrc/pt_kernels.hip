@@ -445,6 +445,8 @@ __global__ void __launch_bounds__(256) adapt_scatter_kernel(const unsigned long 
 
 #include "pt_dev_denoise.h"
 
+#include "pt_dev_temporal.h"
+
 // Multi-device gather, second half: scatter one device's received rows (its bands, in local row
 // order) into the full image.  A band is band-rows consecutive image rows in both buffers, so every
 // lane copies one float4 of a coalesced row.
@@ -543,6 +545,12 @@ struct pt_context {
     float4* dnBuf = nullptr;          // [6][pixels]: colour, two guide planes, two iteration buffers, the result
     hipEvent_t dnEv[12] = {};
     float dnMs[10] = {};
+    // temporal reprojection (pt_temporal.h); no render state
+    pt_camera featCam = {};           // the camera of the last pt_render_features
+    float4* tpBuf = nullptr;          // [8][pixels]: colour, image, two history sets of three planes
+    uint32_t tpSet = 0;               // the set the last pt_temporal wrote
+    pt_camera tpCam = {};             // its camera
+    float tpMs = 0.0f;
     std::string err;
 };
 
@@ -847,6 +855,7 @@ PT_API void pt_destroy(pt_context* ctx)
     (void)hipFree(ctx->adTemp);
     (void)hipFree(ctx->feat);
     (void)hipFree(ctx->dnBuf);
+    (void)hipFree(ctx->tpBuf);
     for (auto& e : ctx->dnEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& t : ctx->hostTex) (void)hipFree((void*)t.texels);
@@ -1954,6 +1963,8 @@ PT_API int pt_set_kernel_variant(pt_context* ctx, int variant)
 } // extern "C"
 
 #include "pt_denoise.h"
+
+#include "pt_temporal.h"
 
 extern "C" PT_API const char* pt_last_error(const pt_context* ctx)
 {
