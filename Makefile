@@ -5,6 +5,8 @@
 #   pathtracercuda_amd/lib/fp_exhaustive  all-inputs check of the kernel's fast 1/x and sqrt (GPU)
 #   pathtracercuda_amd/lib/dev_functions  the kernel's device functions one by one over input files, for
 #                                         tests/test_gpu_dev_functions.py (GPU)
+#   pathtracercuda_amd/lib/ssg_stages     the guess, lane and fold code of speculative sample groups stage by
+#                                         stage over files, for tests/test_gpu_ssg_stages.py (GPU)
 #   pathtracercuda_amd/lib/host_sanitize_check  ASan/UBSan mutation check of the host parsers (CPU)
 #   pathtracercuda_amd/lib/leaf_forms_check  exact vs fast form of the cube leaf test (CPU; `make leafcheck` runs it)
 #   pathtracercuda_amd/lib/launch_plan_check  the launch policy and the build table on the host, for tests/test_launch_plan.py (CPU)
@@ -36,7 +38,7 @@ HIPFLAGS ?= $(HIPCODEGEN) -fPIC -fvisibility=hidden -Iinclude -Wall -Wno-unused-
 CXXFLAGS ?= -O2 -std=c++17 -ffp-contract=off -fno-fast-math -fPIC -Iinclude -I$(SRC)/host -Wall -Wextra \
             -Wno-unused-parameter -Wno-missing-field-initializers
 
-all: $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer $(LIB)/fp_exhaustive $(LIB)/dev_functions $(LIB)/host_sanitize_check $(LIB)/leaf_forms_check $(LIB)/launch_plan_check $(LIB)/ctx_state_check oracle
+all: $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer $(LIB)/fp_exhaustive $(LIB)/dev_functions $(LIB)/ssg_stages $(LIB)/host_sanitize_check $(LIB)/leaf_forms_check $(LIB)/launch_plan_check $(LIB)/ctx_state_check oracle
 
 $(LIB):
 	mkdir -p $(LIB)
@@ -56,6 +58,10 @@ $(LIB)/fp_exhaustive: tools/fp_exhaustive.hip $(SRC)/pt_math.h | $(LIB)
 # The kernel's device functions, one operation per launch, over raw input words (tools/dev_functions.hip).
 $(LIB)/dev_functions: tools/dev_functions.hip $(SRC)/pt_math.h $(SRC)/pt_dev_tex.h $(SRC)/pt_dev_tonemap.h | $(LIB)
 	$(HIPCC) $(HIPCODEGEN) -Wall -o $@ tools/dev_functions.hip
+
+# The sample-group stages on a toy stream (tools/ssg_stages.hip): the kernel's own headers, in its order.
+$(LIB)/ssg_stages: tools/ssg_stages.hip $(wildcard $(SRC)/*.h) include/pt_hip.h | $(LIB)
+	$(HIPCC) $(HIPCODEGEN) -Wall -o $@ tools/ssg_stages.hip
 
 oracle:
 	$(MAKE) -C oracle REF=$(REF)
