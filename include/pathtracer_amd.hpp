@@ -251,6 +251,27 @@ public:
     bool temporal(const TemporalOptions& options, bool reset = false);
     bool temporal() { return temporal(TemporalOptions()); }
     float* getTemporalHDRImageData();
+    // The temporal step with luminance moments and the per-pixel variance estimated from them
+    // (pt_temporal_moments, pt_hip.h): temporal()'s image word for word; temporalVariance returns the variance
+    // (borrowed, rows x width floats, -1 where the pixel is not a finite hit).  denoiseVariance filters the
+    // temporal image with a colour weight that follows that variance (pt_denoise_variance); its result is a
+    // denoised image: the image calls return it as they do denoise()'s.  A history left by temporal() has no
+    // moments: temporalMoments then starts anew and returns false.  Single device only.
+    struct VarianceDenoiseOptions {
+        uint32_t iterations = PT_VDENOISE_DEFAULT_ITERATIONS;
+        float sigmaL = PT_VDENOISE_DEFAULT_SIGMA_L;
+        float varianceFloor = PT_VDENOISE_DEFAULT_VARIANCE_FLOOR;
+        float sigmaPlane = PT_VDENOISE_DEFAULT_SIGMA_PLANE;
+        uint32_t normalPowerLog2 = PT_VDENOISE_DEFAULT_NORMAL_POWER_LOG2;
+        uint32_t flags = PT_VDENOISE_DEFAULT_FLAGS;
+        uint32_t staging = 0;
+    };
+    bool temporalMoments(const TemporalOptions& options, uint32_t minTemporal = PT_VARIANCE_DEFAULT_MIN_TEMPORAL,
+                         bool reset = false);
+    bool temporalMoments() { return temporalMoments(TemporalOptions()); }
+    const float* temporalVariance();
+    void denoiseVariance(const VarianceDenoiseOptions& options);
+    void denoiseVariance() { denoiseVariance(VarianceDenoiseOptions()); }
     float getTiming() const;
     uint32_t loadTexture(const char* path);
     void setSkyboxTextureHandle(uint32_t handle);
@@ -286,6 +307,7 @@ private:
     bool m_denoised = false;
     std::vector<float> m_featureBuffer;
     std::vector<float> m_temporalBuffer;
+    std::vector<float> m_varianceBuffer;
     BVH m_bvh;
     void allocHostBuffers();
     void check(int rc, const char* what) const;

@@ -571,6 +571,114 @@ PT_API int pt_temporal_image(int device, uint32_t width, uint32_t height, const 
                              const pt_temporal_params *params, float *out_image, float *out_hist0, float *out_hist1,
                              float *out_hist2);
 
+/* ---- Per-pixel variance from the temporal history, and the variance-guided filter ------------------
+ * The estimation and filtering of SVGF (Schied et al. 2017) without its feedback: luminance moments are
+ * carried in a fourth history plane, a variance is estimated per pixel, and an a-trous filter takes its
+ * colour weight from that variance instead of one sigma_color for the image.  All float32, no contraction,
+ * + - x /, compares and selects only, in exactly these operations (tests/svgf_model.py restates them).
+ *   lum(c) = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;   "finite" means x - x == 0;
+ *   clamp0(v) = (v > 0 && v finite) ? v : 0
+ *
+ * 1. The temporal step with moments.  pt_temporal's rule unchanged (same pt_temporal_params, same taps, same
+ *    image and h0..h2 word for word) with a fourth history plane  h3 = (m1, m2, v, 0):
+ *     l = lum(I_cur);  q = l * l
+ *     !ok_p:  h3 = (0, 0, -1, 0)
+ *     sumM1 = 0, sumM2 = 0;  in every tap the colour accepts, after its sums:
+ *         sumM1 = sumM1 + w * m1_q;  sumM2 = sumM2 + w * m2_q        (m1_q, m2_q = the previous h3's x, y)
+ *     have:   Hm1 = sumM1 / sumW;  Hm2 = sumM2 / sumW;  m1 = Hm1 + a * (l - Hm1);  m2 = Hm2 + a * (q - Hm2)
+ *     else:   m1 = l, m2 = q
+ *     if m1 or m2 is not finite:  m1 = l, m2 = q                    (the moments restart)
+ *     v = clamp0(m2 - m1 * m1);   h3 = (m1, m2, v, 0)
+ *
+ * 2. The variance estimate, one float per pixel, from the NEW history of the same step (n_p = h0.w,
+ *    I = h0.rgb, N, id = h1, P, t = h2) and its h3:
+ *     n_p < 1 (a pixel that is not ok):  var = -1
+ *     n_p >= (float)min_temporal:        var = h3.z
+ *     otherwise (a young history):  k = 0, s1 = 0, s2 = 0;  m = sigma_plane * t_p;  mm = m * m
+ *       for dy = -3 .. 3 (outer), dx = -3 .. 3 (inner), q = p + (dx, dy):
+ *       the centre tap (dx = dy = 0) always counts; any other tap is skipped (by a select; its index is
+ *       clamped into the image before the load) when q is outside the image, or n_q < 1, or
+ *       N_p . N_q < normal_cos_min, or with g = N_p . (P_q - P_p)  !(g*g <= mm), or SAME_PRIMITIVE is set
+ *       and id_q != id_p;  otherwise
+ *         lq = lum(I_q);  k = k + 1;  s1 = s1 + lq;  s2 = s2 + lq * lq
+ *       mean = s1 / k;  vs = clamp0(s2 / k - mean * mean);  var = vs * ((float)min_temporal / n_p)
+ *    min_temporal 1..255 (pt_variance_params); anything else is PT_ERR_ARG naming the field.
+ *
+ * 3. The variance-guided filter.  pt_denoise's structure (prepare, one launch per iteration between two
+ *    buffers, finish; 32 x 8 tile; staged and unstaged forms with the same words), with these changes:
+ *    Prepare:  keep_p = pt_denoise's keep_p && var_p >= 0 && var_p finite && lum(I_p) finite
+ *              v_p = var_p < 2^60 ? var_p : 2^60;   the texel is (I_p, keep_p ? v_p : -1)
+ *              "kept" below means: the texel's w is not < 0
+ *    Iteration i, step s = 1 << i (sigma_l is the same at every level), for a kept p:
+ *       sumG = 0, sumV = 0;  for dy = -1 .. 1 (outer), dx = -1 .. 1 (inner), q = p + (dx, dy) (unit spacing):
+ *         q is skipped (by a select) when it is outside the image or not kept;  otherwise
+ *         g = k3[|dx|] * k3[|dy|],  k3 = {1/2, 1/4};  sumG = sumG + g;  sumV = sumV + g * v_q
+ *       vg = sumV / sumG;  den = (sigma_l * sigma_l) * vg + variance_floor;  lp = lum(I_p)
+ *       sumW = 0, sumI = (0, 0, 0), sumV2 = 0;  the 25 taps q = p + s * (dx, dy) in pt_denoise's order, with
+ *       its skips (outside, not kept, SAME_PRIMITIVE) and its h, w_n, w_p and mm:
+ *         d = lum(I_q) - lp;  w_c = 1 / (1 + (d * d) / den);  w = ((h * w_n) * w_p) * w_c
+ *         sumW = sumW + w;  sumI = sumI + w * I_q (per channel);  sumV2 = sumV2 + (w * w) * v_q
+ *       I'_p = sumI / sumW;  v'_p = sumV2 / (sumW * sumW)
+ *    A pixel that is not kept is handed on unchanged.
+ *    Final:  out_p = kept ? I_p * D_p : C_p;  out.w = 1
+ *    Accepted: iterations 1..8, sigma_l in (0, 2^20], variance_floor > 0 and finite, sigma_plane >= 1e-6 and
+ *    finite, normal_power_log2 0..7, flags within the two denoise bits, staging 0..2 (as pt_denoise's);
+ *    anything else (a NaN included) is PT_ERR_ARG and the message names the field.  With v <= 2^60 and
+ *    sigma_l <= 2^20 the product (sigma_l * sigma_l) * vg is at most 2^100: den never overflows. */
+/* Defaults of the layers above (C++ Pathtracer::temporalMoments / denoiseVariance, Python), chosen by the
+ * sweep of tools/svgf_probe.py (profiles/svgf_probe.json); sigma_plane, normal_power_log2
+ * and flags are pt_denoise's. */
+#define PT_VARIANCE_DEFAULT_MIN_TEMPORAL 4
+#define PT_VDENOISE_DEFAULT_ITERATIONS 5
+#define PT_VDENOISE_DEFAULT_SIGMA_L 16.0f
+#define PT_VDENOISE_DEFAULT_VARIANCE_FLOOR 1e-4f
+#define PT_VDENOISE_DEFAULT_SIGMA_PLANE 0.005f
+#define PT_VDENOISE_DEFAULT_NORMAL_POWER_LOG2 3
+#define PT_VDENOISE_DEFAULT_FLAGS 1u
+typedef struct pt_variance_params {
+    uint32_t min_temporal;   /* history length from which the temporal variance is trusted */
+} pt_variance_params;
+typedef struct pt_vdenoise_params {
+    uint32_t iterations;
+    float sigma_l;           /* in standard deviations of the luminance */
+    float variance_floor;
+    float sigma_plane;       /* relative to the hit distance */
+    uint32_t normal_power_log2;
+    uint32_t flags;          /* PT_DENOISE_DEMODULATE, PT_DENOISE_SAME_PRIMITIVE */
+    uint32_t staging;
+} pt_vdenoise_params;
+
+/* pt_temporal with moments and the variance estimate, on the context: arguments, refusals and results as
+ * pt_temporal's, and the image and history planes 0..2 are word for word those pt_temporal gives.  The
+ * moments planes and the variance are a separate allocation, made on first use.  "The held history has
+ * moments" from the end of this call until whatever ends the history, or a pt_temporal step (which may still
+ * reproject the colour history of this one: planes 0..2 have one layout); a call that meets a history
+ * without moments acts as reset (history_used = 0). */
+PT_API int pt_temporal_moments(pt_context *ctx, uint32_t frames, const pt_temporal_params *params,
+                               const pt_variance_params *variance, int reset, int *history_used);
+/* The variance of the last pt_temporal_moments (rows x width float) and the hipEvent times in ms of its two
+ * kernels (step, estimate).  PT_ERR_STATE unless a moments step has finished and its history is still held. */
+PT_API int pt_read_temporal_variance(pt_context *ctx, float *dst);
+PT_API int pt_read_temporal_moments_timing(pt_context *ctx, float *dst);
+/* The variance-guided filter of the temporal image with the variance of the same step; the result goes where
+ * pt_denoise's goes (pt_read_denoised, pt_tonemap_denoised, pt_read_denoise_timing).  PT_ERR_STATE, naming
+ * the reason, without a held variance or when pt_render_features has run since; PT_ERR_ARG when the
+ * DEMODULATE bit differs from the one the moments were made with. */
+PT_API int pt_denoise_variance(pt_context *ctx, const pt_vdenoise_params *params);
+/* The same on host arrays, without a context (as pt_temporal_image, pt_denoise_image): hist3 and out_hist3
+ * are height x width float4, out_variance and variance height x width float.  hist0 = NULL means no
+ * previous history.  pt_denoise_variance_image takes a variance from any source.  Errors: pt_last_error(NULL). */
+PT_API int pt_temporal_moments_image(int device, uint32_t width, uint32_t height, const float *color,
+                                     const float *plane0, const float *plane1, const float *plane2,
+                                     const pt_camera *cur_cam, const float *hist0, const float *hist1,
+                                     const float *hist2, const float *hist3, const pt_camera *prev_cam,
+                                     const pt_temporal_params *params, const pt_variance_params *variance,
+                                     float *out_image, float *out_hist0, float *out_hist1, float *out_hist2,
+                                     float *out_hist3, float *out_variance);
+PT_API int pt_denoise_variance_image(int device, uint32_t width, uint32_t height, const float *color,
+                                     const float *plane0, const float *plane1, const float *plane2,
+                                     const float *variance, const pt_vdenoise_params *params, float *out);
+
 /* ---- Multi-device group (one process, one context per GPU, RCCL over xGMI) -------------------
  * Replaces the reference's hard-coded single device (Pathtracer.cpp:40: cudaSetDevice(0)) behind
  * the same Pathtracer interface: device i renders the row bands b = i, i + N, ... of the image

@@ -97,6 +97,14 @@ PT_API int pth_renderer_denoised(const pth_renderer *r);
  * are not changed by either. */
 PT_API int pth_renderer_temporal(pth_renderer *r, const pt_temporal_params *params, int reset, int *history_used);
 PT_API const float *pth_renderer_temporal_hdr(pth_renderer *r);
+/* Pathtracer::temporalMoments / temporalVariance / denoiseVariance (pt_temporal_moments, pt_denoise_variance,
+ * pt_hip.h; single device).  pth_renderer_temporal_variance: a borrowed pointer (rows x width floats) valid
+ * until the next call, null on error.  After pth_renderer_denoise_variance pth_renderer_hdr /
+ * pth_renderer_image return the filtered image, and pth_renderer_denoised is 1, as after pth_renderer_denoise. */
+PT_API int pth_renderer_temporal_moments(pth_renderer *r, const pt_temporal_params *params,
+                                         const pt_variance_params *variance, int reset, int *history_used);
+PT_API const float *pth_renderer_temporal_variance(pth_renderer *r);
+PT_API int pth_renderer_denoise_variance(pth_renderer *r, const pt_vdenoise_params *params);
 PT_API float pth_renderer_timing(const pth_renderer *r);
 PT_API uint32_t pth_renderer_frames(const pth_renderer *r);
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer *r);

@@ -27,7 +27,8 @@ from ._native import PathtracerError, PtBvhNode, PtCamera, PtHittable, PtRenderS
 __all__ = ["Pathtracer", "Scene", "make_camera", "camera_rotate", "camera_translate", "radians", "device_count", "PathtracerError", "PtCamera",
            "PtBvhNode", "PtHittable", "write_png", "write_hdr", "HITTABLE_TYPES", "MATERIAL_TYPES", "denoise_image",
            "denoise_params", "auto_sigma_color", "denoise_keep_mask", "DENOISE_DEFAULTS", "DENOISE_SIGMA_FACTOR",
-           "temporal_params", "temporal_image", "TEMPORAL_DEFAULTS"]
+           "temporal_params", "temporal_image", "TEMPORAL_DEFAULTS", "variance_params", "vdenoise_params",
+           "temporal_moments_image", "denoise_variance_image", "VARIANCE_DEFAULTS", "VDENOISE_DEFAULTS"]
 
 HITTABLE_TYPES = ["SPHERE", "CYLINDER", "DISK", "CONE", "PARABOLOID", "QUAD", "CUBE"]   # Hittable.h:9-12
 MATERIAL_TYPES = ["LAMBERT", "GGX", "LAMBERT_GGX"]                                     # Material.h:9-12
@@ -226,6 +227,115 @@ def temporal_image(color, plane0, plane1, plane2, cur_camera: PtCamera, history=
                                    C.byref(params), *[o.ctypes.data_as(fp) for o in outs])
     N.check_ctx(rc, None)
     return tuple(outs)
+
+
+# Defaults of the variance estimate and the variance-guided filter (PT_VARIANCE_DEFAULT_*, PT_VDENOISE_DEFAULT_*
+# of include/pt_hip.h), chosen by the sweep of tools/svgf_probe.py (profiles/svgf_probe.json).
+VARIANCE_DEFAULTS = {"min_temporal": 4}
+VDENOISE_DEFAULTS = {"iterations": 5, "sigma_l": 16.0, "variance_floor": 1e-4, "sigma_plane": 0.005,
+                     "normal_power_log2": 3, "demodulate": True, "same_primitive": False}
+
+
+def variance_params(min_temporal: Optional[int] = None) -> "N.PtVarianceParams":
+    """pt_variance_params, refused here (PT_ERR_ARG naming the field) when out of range."""
+    min_temporal = VARIANCE_DEFAULTS["min_temporal"] if min_temporal is None else min_temporal
+    if isinstance(min_temporal, float) and not np.isfinite(min_temporal):
+        raise _refuse(f"temporal: min_temporal must be 1..255, not {min_temporal!r}")
+    if int(min_temporal) != min_temporal or not 1 <= int(min_temporal) <= 255:
+        raise _refuse(f"temporal: min_temporal must be 1..255, not {min_temporal!r}")
+    return N.PtVarianceParams(int(min_temporal))
+
+
+def vdenoise_params(iterations: Optional[int] = None, sigma_l: Optional[float] = None,
+                    variance_floor: Optional[float] = None, sigma_plane: Optional[float] = None,
+                    normal_power_log2: Optional[int] = None, demodulate: Optional[bool] = None,
+                    same_primitive: Optional[bool] = None, staging: int = 0) -> "N.PtVDenoiseParams":
+    """pt_vdenoise_params from keyword arguments, refused here (PT_ERR_ARG naming the field) before any
+    device call when a value is outside the accepted range of include/pt_hip.h."""
+    d = VDENOISE_DEFAULTS
+    iterations = d["iterations"] if iterations is None else iterations
+    sigma_l = d["sigma_l"] if sigma_l is None else sigma_l
+    variance_floor = d["variance_floor"] if variance_floor is None else variance_floor
+    sigma_plane = d["sigma_plane"] if sigma_plane is None else sigma_plane
+    normal_power_log2 = d["normal_power_log2"] if normal_power_log2 is None else normal_power_log2
+    demodulate = d["demodulate"] if demodulate is None else demodulate
+    same_primitive = d["same_primitive"] if same_primitive is None else same_primitive
+    if int(iterations) != iterations or not 1 <= int(iterations) <= 8:
+        raise _refuse(f"denoise: iterations must be 1..8, not {iterations!r}")
+    sl, vf, sp = np.float32(sigma_l), np.float32(variance_floor), np.float32(sigma_plane)
+    if not (sl > 0 and sl <= np.float32(2.0 ** 20)):
+        raise _refuse(f"denoise: sigma_l must be in (0, 2^20], not {sigma_l!r}")
+    if not (vf > 0 and np.isfinite(vf)):
+        raise _refuse(f"denoise: variance_floor must be > 0 and finite, not {variance_floor!r}")
+    if not (sp >= np.float32(1e-6) and np.isfinite(sp)):
+        raise _refuse(f"denoise: sigma_plane must be >= 1e-6 and finite, not {sigma_plane!r}")
+    if int(normal_power_log2) != normal_power_log2 or not 0 <= int(normal_power_log2) <= 7:
+        raise _refuse(f"denoise: normal_power_log2 must be 0..7, not {normal_power_log2!r}")
+    if staging not in (0, 1, 2):
+        raise _refuse(f"denoise: staging must be 0, 1 or 2, not {staging!r}")
+    flags = (N.PT_DENOISE_DEMODULATE if demodulate else 0) | (N.PT_DENOISE_SAME_PRIMITIVE if same_primitive else 0)
+    return N.PtVDenoiseParams(int(iterations), float(sl), float(vf), float(sp), int(normal_power_log2), flags, int(staging))
+
+
+def _image1(name: str, a, shape) -> np.ndarray:
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.shape != shape[:2]:
+        raise _refuse(f"denoise_variance_image: {name} has shape {a.shape}, color has {shape}")
+    return a
+
+
+def temporal_moments_image(color, plane0, plane1, plane2, cur_camera: PtCamera, history=None,
+                           prev_camera: Optional[PtCamera] = None, alpha_min: Optional[float] = None,
+                           max_history: Optional[int] = None, sigma_plane: Optional[float] = None,
+                           normal_cos_min: Optional[float] = None, demodulate: Optional[bool] = None,
+                           same_primitive: Optional[bool] = None, min_temporal: Optional[int] = None, device: int = 0):
+    """pt_temporal_moments_image: temporal_image() with the moments plane and the variance estimate.
+    `history` = the (h0, h1, h2, h3) an earlier step returned, or None.  Returns (image, h0, h1, h2, h3,
+    variance); variance is height x width float32, -1 where the pixel is not a finite hit."""
+    params = temporal_params(alpha_min, max_history, sigma_plane, normal_cos_min, demodulate, same_primitive)
+    vparams = variance_params(min_temporal)
+    c = _image4("color", color)
+    arrays = [c] + [_image4(f"plane{k}", p, c.shape) for k, p in enumerate((plane0, plane1, plane2))]
+    fp = C.POINTER(C.c_float)
+    null = C.cast(None, fp)
+    if history is not None:
+        if prev_camera is None:
+            raise _refuse("temporal_moments_image: history is given without prev_camera")
+        hist = [_image4(f"history[{k}]", h, c.shape) for k, h in enumerate(history)]
+        if len(hist) != 4:
+            raise _refuse("temporal_moments_image: history must be (h0, h1, h2, h3)")
+        hp = [h.ctypes.data_as(fp) for h in hist]
+    else:
+        hp = [null, null, null, null]
+    outs = [np.zeros_like(c) for _ in range(5)] + [np.zeros(c.shape[:2], dtype=np.float32)]
+    rc = N.hip().pt_temporal_moments_image(int(device), c.shape[1], c.shape[0], *[a.ctypes.data_as(fp) for a in arrays],
+                                           C.byref(cur_camera), *hp,
+                                           C.byref(prev_camera) if prev_camera is not None else None, C.byref(params),
+                                           C.byref(vparams), *[o.ctypes.data_as(fp) for o in outs])
+    N.check_ctx(rc, None)
+    return tuple(outs)
+
+
+def denoise_variance_image(color, plane0, plane1, plane2, variance, iterations: Optional[int] = None,
+                           sigma_l: Optional[float] = None, variance_floor: Optional[float] = None,
+                           sigma_plane: Optional[float] = None, normal_power_log2: Optional[int] = None,
+                           demodulate: Optional[bool] = None, same_primitive: Optional[bool] = None, staging: int = 0,
+                           device: int = 0) -> np.ndarray:
+    """pt_denoise_variance_image: the variance-guided a-trous filter of include/pt_hip.h on host arrays, without
+    a Pathtracer.  `variance` is height x width float32, of the luminance of the (demodulated, when demodulating)
+    colour, from any source; a pixel whose variance is negative or not finite passes through."""
+    params = vdenoise_params(iterations, sigma_l, variance_floor, sigma_plane, normal_power_log2, demodulate,
+                             same_primitive, staging)
+    c = _image4("color", color)
+    planes = [_image4(f"plane{k}", p, c.shape) for k, p in enumerate((plane0, plane1, plane2))]
+    var = _image1("variance", variance, c.shape)
+    out = np.zeros_like(c)
+    fp = C.POINTER(C.c_float)
+    rc = N.hip().pt_denoise_variance_image(int(device), c.shape[1], c.shape[0], c.ctypes.data_as(fp),
+                                           *[p.ctypes.data_as(fp) for p in planes], var.ctypes.data_as(fp),
+                                           C.byref(params), out.ctypes.data_as(fp))
+    N.check_ctx(rc, None)
+    return out
 
 
 class Scene:
@@ -443,7 +553,8 @@ class Pathtracer:
     def denoise(self, iterations: int = 5, sigma_color: Optional[float] = None, sigma_plane: Optional[float] = None,
                 normal_power_log2: Optional[int] = None, demodulate: Optional[bool] = None,
                 same_primitive: Optional[bool] = None, staging: int = 0, frames: Optional[int] = None,
-                source: str = "accumulation") -> np.ndarray:
+                source: str = "accumulation", guide: str = "color", sigma_l: Optional[float] = None,
+                variance_floor: Optional[float] = None) -> np.ndarray:
         """Filter the image with the edge-avoiding a-trous denoiser (include/pt_hip.h), guided by the
         planes of the last features(camera) call; returns rows x width x 4 float32 in
         get_hdr_image_data()'s units and leaves the accumulation as it is.  sigma_color=None: a factor times
@@ -451,10 +562,26 @@ class Pathtracer:
         accumulation (default: the frame counter; an adaptive render divides every pixel by its own count).
         source="temporal": the image of the last temporal() is filtered instead (pt_denoise_temporal), guided
         by the planes it was made from; the automatic sigma is then of that image.
+        guide="variance" (with source="temporal", after temporal(variance=True)): the colour weight follows the
+        per-pixel variance of that step instead of one sigma_color (pt_denoise_variance); sigma_l is in
+        standard deviations of the luminance, variance_floor keeps the weight defined where the variance is 0.
         Arguments out of range raise before any device call."""
         self._single("denoise")
         if source not in ("accumulation", "temporal"):
             raise _refuse(f"denoise: source must be 'accumulation' or 'temporal', not {source!r}")
+        if guide not in ("color", "variance"):
+            raise _refuse(f"denoise: guide must be 'color' or 'variance', not {guide!r}")
+        if guide == "variance":
+            if source != "temporal":
+                raise _refuse("denoise: guide='variance' needs source='temporal' (the variance is the temporal history's)")
+            if sigma_color is not None:
+                raise _refuse("denoise: sigma_color is not used with guide='variance' (give sigma_l)")
+            vparams = vdenoise_params(iterations, sigma_l, variance_floor, sigma_plane, normal_power_log2, demodulate,
+                                      same_primitive, staging)
+            N.check_ctx(N.hip().pt_denoise_variance(self._ctx, C.byref(vparams)), self._ctx)
+            return self.denoised()
+        if sigma_l is not None or variance_floor is not None:
+            raise _refuse("denoise: sigma_l and variance_floor are given without guide='variance'")
         demod = DENOISE_DEFAULTS["demodulate"] if demodulate is None else demodulate
         params = denoise_params(iterations, 1.0 if sigma_color is None else sigma_color, sigma_plane, normal_power_log2,
                                 demod, same_primitive, staging)
@@ -507,21 +634,48 @@ class Pathtracer:
     # --- temporal reprojection (pt_temporal; pt_hip.h) ---------------------------------------------
     def temporal(self, alpha_min: Optional[float] = None, max_history: Optional[int] = None,
                  sigma_plane: Optional[float] = None, normal_cos_min: Optional[float] = None, demodulate: Optional[bool] = None,
-                 same_primitive: Optional[bool] = None, reset: bool = False, frames: Optional[int] = None) -> np.ndarray:
+                 same_primitive: Optional[bool] = None, reset: bool = False, frames: Optional[int] = None,
+                 variance: bool = False, min_temporal: Optional[int] = None) -> np.ndarray:
         """One step of temporal accumulation (include/pt_hip.h): the result of the previous temporal() is
         reprojected into the camera of the last features(camera) through its planes, rejected where it is no
         longer the same surface, and the current image blended in.  Call order per frame:
         render(cam, spp, True), features(cam), temporal().  Returns the image, rows x width x 4 float32 in
         get_hdr_image_data()'s units with w = the history length; `history_used` tells whether a previous
         history was held (none after reset=True, a scene load, a texture or another sky).  Touches nothing of
-        the render state.  Arguments out of range raise before any device call."""
+        the render state.  Arguments out of range raise before any device call.
+        variance=True (pt_temporal_moments): the same image word for word, and luminance moments are carried in
+        the history and a per-pixel variance estimated from them (temporal_variance(); min_temporal = the
+        history length from which the temporal estimate is trusted); a history left by a step without
+        variance is not used."""
         self._single("temporal")
         params = temporal_params(alpha_min, max_history, sigma_plane, normal_cos_min, demodulate, same_primitive)
         f = self.frames if frames is None else int(frames)
         used = C.c_int(0)
-        N.check_ctx(N.hip().pt_temporal(self._ctx, f, C.byref(params), int(bool(reset)), C.byref(used)), self._ctx)
+        if variance:
+            vparams = variance_params(min_temporal)
+            N.check_ctx(N.hip().pt_temporal_moments(self._ctx, f, C.byref(params), C.byref(vparams), int(bool(reset)),
+                                                    C.byref(used)), self._ctx)
+        else:
+            if min_temporal is not None:
+                raise _refuse("temporal: min_temporal is given without variance=True")
+            N.check_ctx(N.hip().pt_temporal(self._ctx, f, C.byref(params), int(bool(reset)), C.byref(used)), self._ctx)
         self.history_used = bool(used.value)
         return self.temporal_image()
+
+    def temporal_variance(self) -> np.ndarray:
+        """The per-pixel variance of the last temporal(variance=True) (pt_read_temporal_variance): rows x width
+        float32, of the luminance of the (demodulated) colour; -1 where the pixel is not a finite hit."""
+        self._single("temporal_variance")
+        out = np.zeros((self.rows, self.width), dtype=np.float32)
+        N.check_ctx(N.hip().pt_read_temporal_variance(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float))), self._ctx)
+        return out
+
+    def temporal_moments_timing(self) -> Dict[str, float]:
+        """Kernel times of the last temporal(variance=True) in ms (hipEvents): {"step", "estimate"}."""
+        self._single("temporal_moments_timing")
+        ms = (C.c_float * 2)()
+        N.check_ctx(N.hip().pt_read_temporal_moments_timing(self._ctx, ms), self._ctx)
+        return {"step": float(ms[0]), "estimate": float(ms[1])}
 
     def temporal_image(self) -> np.ndarray:
         """The last temporal()'s image again (pt_read_temporal)."""

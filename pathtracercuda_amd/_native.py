@@ -73,6 +73,18 @@ class PtTemporalParams(C.Structure):
                 ("normal_cos_min", C.c_float), ("flags", C.c_uint32)]
 
 
+class PtVarianceParams(C.Structure):
+    """pt_variance_params (pt_hip.h, the variance estimate of the temporal history)."""
+    _fields_ = [("min_temporal", C.c_uint32)]
+
+
+class PtVDenoiseParams(C.Structure):
+    """pt_vdenoise_params (pt_hip.h, variance-guided a-trous filter)."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_l", C.c_float), ("variance_floor", C.c_float),
+                ("sigma_plane", C.c_float), ("normal_power_log2", C.c_uint32), ("flags", C.c_uint32),
+                ("staging", C.c_uint32)]
+
+
 PT_FEATURE_HIT, PT_FEATURE_EMISSIVE = 1, 2
 PT_TEMPORAL_DEMODULATE, PT_TEMPORAL_SAME_PRIMITIVE = 1, 2
 PT_DENOISE_DEMODULATE, PT_DENOISE_SAME_PRIMITIVE = 1, 2
@@ -148,6 +160,15 @@ _HIP_SYMBOLS = {
     "pt_temporal_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
                                     P(PtCamera), P(C.c_float), P(C.c_float), P(C.c_float), P(PtCamera), P(PtTemporalParams),
                                     P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float)]),
+    "pt_temporal_moments": (C.c_int, [C.c_void_p, C.c_uint32, P(PtTemporalParams), P(PtVarianceParams), C.c_int, P(C.c_int)]),
+    "pt_read_temporal_variance": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_read_temporal_moments_timing": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_denoise_variance": (C.c_int, [C.c_void_p, P(PtVDenoiseParams)]),
+    "pt_temporal_moments_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 4 + [P(PtCamera)]
+                                  + [P(C.c_float)] * 4 + [P(PtCamera), P(PtTemporalParams), P(PtVarianceParams)]
+                                  + [P(C.c_float)] * 6),
+    "pt_denoise_variance_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 5
+                                  + [P(PtVDenoiseParams), P(C.c_float)]),
     "pt_group_create": (C.c_int, [C.c_int, P(C.c_int), C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_void_p)]),
     "pt_group_destroy": (None, [C.c_void_p]),
     "pt_group_size": (C.c_int, [C.c_void_p]),
@@ -197,6 +218,9 @@ _HOST_SYMBOLS = {
     "pth_renderer_denoised": (C.c_int, [C.c_void_p]),
     "pth_renderer_temporal": (C.c_int, [C.c_void_p, P(PtTemporalParams), C.c_int, P(C.c_int)]),
     "pth_renderer_temporal_hdr": (P(C.c_float), [C.c_void_p]),
+    "pth_renderer_temporal_moments": (C.c_int, [C.c_void_p, P(PtTemporalParams), P(PtVarianceParams), C.c_int, P(C.c_int)]),
+    "pth_renderer_temporal_variance": (P(C.c_float), [C.c_void_p]),
+    "pth_renderer_denoise_variance": (C.c_int, [C.c_void_p, P(PtVDenoiseParams)]),
     "pth_renderer_timing": (C.c_float, [C.c_void_p]),
     "pth_renderer_frames": (C.c_uint32, [C.c_void_p]),
     "pth_renderer_local_rows": (C.c_uint32, [C.c_void_p]),

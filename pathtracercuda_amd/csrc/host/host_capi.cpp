@@ -362,6 +362,48 @@ PT_API const float* pth_renderer_temporal_hdr(pth_renderer* r)
     return nullptr;
 }
 
+PT_API int pth_renderer_temporal_moments(pth_renderer* r, const pt_temporal_params* params, const pt_variance_params* variance,
+                                         int reset, int* history_used)
+{
+    if (!r || !params || !variance) return setError(PT_ERR_ARG, "invalid argument");
+    PTH_GUARD_BEGIN
+    Pathtracer::TemporalOptions o;
+    o.alphaMin = params->alpha_min;
+    o.maxHistory = params->max_history;
+    o.sigmaPlane = params->sigma_plane;
+    o.normalCosMin = params->normal_cos_min;
+    o.flags = params->flags;
+    const bool used = r->pt->temporalMoments(o, variance->min_temporal, reset != 0);
+    if (history_used) *history_used = used ? 1 : 0;
+    return PT_OK;
+    PTH_GUARD_END
+}
+
+PT_API const float* pth_renderer_temporal_variance(pth_renderer* r)
+{
+    if (!r) return nullptr;
+    ptamd::g_throwOnError = true;
+    try { return r->pt->temporalVariance(); } catch (const std::exception& e) { setError(PT_ERR_STATE, e.what()); }
+    return nullptr;
+}
+
+PT_API int pth_renderer_denoise_variance(pth_renderer* r, const pt_vdenoise_params* params)
+{
+    if (!r || !params) return setError(PT_ERR_ARG, "invalid argument");
+    PTH_GUARD_BEGIN
+    Pathtracer::VarianceDenoiseOptions o;
+    o.iterations = params->iterations;
+    o.sigmaL = params->sigma_l;
+    o.varianceFloor = params->variance_floor;
+    o.sigmaPlane = params->sigma_plane;
+    o.normalPowerLog2 = params->normal_power_log2;
+    o.flags = params->flags;
+    o.staging = params->staging;
+    r->pt->denoiseVariance(o);
+    return PT_OK;
+    PTH_GUARD_END
+}
+
 PT_API float pth_renderer_timing(const pth_renderer* r) { return r ? r->pt->getTiming() : 0.0f; }
 PT_API uint32_t pth_renderer_frames(const pth_renderer* r) { return r ? r->pt->accumulatedFrames() : 0; }
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer* r) { return r ? r->pt->localRows() : 0; }

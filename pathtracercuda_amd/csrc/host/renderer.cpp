@@ -228,6 +228,32 @@ float* Pathtracer::getTemporalHDRImageData()
     return m_temporalBuffer.data();
 }
 
+bool Pathtracer::temporalMoments(const TemporalOptions& o, uint32_t minTemporal, bool reset)
+{
+    if (m_group) check(PT_ERR_STATE, "temporalMoments: not available on a device group");
+    const pt_temporal_params p = {o.alphaMin, o.maxHistory, o.sigmaPlane, o.normalCosMin, o.flags};
+    const pt_variance_params v = {minTemporal};
+    int used = 0;
+    check(pt_temporal_moments(m_ctx, m_accumulatedFrames, &p, &v, reset ? 1 : 0, &used), "pt_temporal_moments");
+    return used != 0;
+}
+
+const float* Pathtracer::temporalVariance()
+{
+    if (m_group) check(PT_ERR_STATE, "temporalVariance: not available on a device group");
+    m_varianceBuffer.resize((size_t)localRows() * m_width);
+    check(pt_read_temporal_variance(m_ctx, m_varianceBuffer.data()), "pt_read_temporal_variance");
+    return m_varianceBuffer.data();
+}
+
+void Pathtracer::denoiseVariance(const VarianceDenoiseOptions& o)
+{
+    if (m_group) check(PT_ERR_STATE, "denoiseVariance: not available on a device group");
+    const pt_vdenoise_params p = {o.iterations, o.sigmaL, o.varianceFloor, o.sigmaPlane, o.normalPowerLog2, o.flags, o.staging};
+    check(pt_denoise_variance(m_ctx, &p), "pt_denoise_variance");
+    m_denoised = true;
+}
+
 float Pathtracer::getTiming() const { return m_timing; }
 
 uint32_t Pathtracer::loadTexture(const char* path)

@@ -1,5 +1,5 @@
 // pt_ctx_state.h -- what a context carries from one call to the next, and every rule that moves it:
-// no HIP call, no context, plain values.  The C ABI functions (pt_kernels.hip, pt_denoise.h, pt_temporal.h)
+// no HIP call, no context, plain values.  The C ABI functions (pt_kernels.hip, pt_denoise.h, pt_temporal.h, pt_svgf.h)
 // raise the events below and ask the predicates; they assign none of these fields themselves.
 // tools/ctx_state_check.cpp and tests/test_ctx_state.py run the same functions on the CPU.
 //
@@ -34,6 +34,10 @@
 //   tpOfPlanes      the temporal image was made from the planes the context holds now (pt_denoise_temporal's
 //                   guide): set when a temporal pass is done, ended by its beginning and by the beginning
 //                   of a features call.  Implies tpValid.
+//   momValid        the held history has moments (a fourth plane, and the variance estimated from it:
+//                   pt_temporal_moments, pt_read_temporal_variance, pt_denoise_variance): set when a moments
+//                   step is done, ended by whatever ends the history -- a pt_temporal step included, which
+//                   begins as every temporal pass and sets it no more.  Implies histValid.
 //   epoch           counts the launches that wrote the accumulation (a device group's gather cache
 //                   key, pt_group.h).  Never decreases.
 // A call refused for its arguments or for the state raises no event (but for a render whose plan is a
@@ -56,6 +60,7 @@ struct CtxState {
     bool adMomValid = false, adCountsValid = false;
     bool featValid = false, dnValid = false;
     bool tpValid = false, histValid = false, tpOfPlanes = false;
+    bool momValid = false;
     uint64_t epoch = 0;
 };
 
@@ -67,6 +72,7 @@ inline void scene_or_texture_changed(CtxState& s)
     s.adMomValid = false;
     s.featValid = false;
     s.histValid = false;
+    s.momValid = false;
     ++s.stateEpoch;
 }
 
@@ -78,6 +84,7 @@ inline void sky_set(CtxState& s, uint32_t held, uint32_t handle)
     ++s.stateEpoch;
     s.adMomValid = false;
     s.histValid = false;
+    s.momValid = false;
 }
 
 // pt_write_rng: a stash and the moments continue the old streams
@@ -169,6 +176,7 @@ inline void temporal_begins(CtxState& s)
     s.tpValid = false;
     s.histValid = false;
     s.tpOfPlanes = false;
+    s.momValid = false;
 }
 inline void temporal_done(CtxState& s)
 {
@@ -176,6 +184,8 @@ inline void temporal_done(CtxState& s)
     s.histValid = true;
     s.tpOfPlanes = true;
 }
+// a moments step raises temporal_begins, temporal_done and then this
+inline void moments_done(CtxState& s) { s.momValid = s.histValid; }
 
 // ---- predicates -----------------------------------------------------------------------------------
 inline bool counts_describe_buffer(const CtxState& s) { return s.adCountsValid; }
@@ -185,5 +195,6 @@ inline bool holds_denoised(const CtxState& s) { return s.dnValid; }
 inline bool holds_temporal(const CtxState& s) { return s.tpValid; }
 inline bool history_held(const CtxState& s) { return s.histValid; }
 inline bool temporal_of_planes(const CtxState& s) { return s.tpOfPlanes; }
+inline bool history_has_moments(const CtxState& s) { return s.momValid; }
 
 } // namespace pt

@@ -447,6 +447,8 @@ __global__ void __launch_bounds__(256) adapt_scatter_kernel(const unsigned long 
 
 #include "pt_dev_temporal.h"
 
+#include "pt_dev_svgf.h"
+
 // Multi-device gather, second half: scatter one device's received rows (its bands, in local row
 // order) into the full image.  A band is band-rows consecutive image rows in both buffers, so every
 // lane copies one float4 of a coalesced row.
@@ -551,6 +553,11 @@ struct pt_context {
     uint32_t tpSet = 0;               // the set the last pt_temporal wrote
     pt_camera tpCam = {};             // its camera
     float tpMs = 0.0f;
+    // the history's moments and the variance (pt_svgf.h); no render state
+    float4* tmBuf = nullptr;          // [2][pixels] moments planes of tpBuf's two history sets, then [pixels] float: the variance
+    hipEvent_t tmEv[3] = {};
+    float tmMs[2] = {};               // the step, the estimate
+    uint32_t tmFlags = 0;             // the flags the held moments were made with
     std::string err;
 };
 
@@ -856,7 +863,10 @@ PT_API void pt_destroy(pt_context* ctx)
     (void)hipFree(ctx->feat);
     (void)hipFree(ctx->dnBuf);
     (void)hipFree(ctx->tpBuf);
+    (void)hipFree(ctx->tmBuf);
     for (auto& e : ctx->dnEv)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : ctx->tmEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& t : ctx->hostTex) (void)hipFree((void*)t.texels);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -1965,6 +1975,8 @@ PT_API int pt_set_kernel_variant(pt_context* ctx, int variant)
 #include "pt_denoise.h"
 
 #include "pt_temporal.h"
+
+#include "pt_svgf.h"
 
 extern "C" PT_API const char* pt_last_error(const pt_context* ctx)
 {

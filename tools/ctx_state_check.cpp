@@ -43,11 +43,11 @@ static pt_camera camera_of(unsigned long long id)
 static void (*const kEventFns[])(CtxState&) = {
     scene_or_texture_changed, rng_written, schedule_changed, order_dropped, order_replaced, order_biased,
     accum_written, stash_made, adaptive_begins, adaptive_done, features_begin, features_done, denoise_begins, denoise_done,
-    temporal_begins, temporal_done};
+    temporal_begins, temporal_done, moments_done};
 static const char* const kEventNames[] = {
     "scene_or_texture_changed", "rng_written", "schedule_changed", "order_dropped", "order_replaced",
     "order_biased", "accum_written", "stash_made", "adaptive_begins", "adaptive_done", "features_begin", "features_done",
-    "denoise_begins", "denoise_done", "temporal_begins", "temporal_done"};
+    "denoise_begins", "denoise_done", "temporal_begins", "temporal_done", "moments_done"};
 constexpr int kEvents = sizeof(kEventFns) / sizeof(kEventFns[0]);
 // the tool's own list of the events after which a sample is no longer what the last render's was
 static bool moves_epoch(void (*event)(CtxState&))
@@ -57,9 +57,9 @@ static bool moves_epoch(void (*event)(CtxState&))
 static_assert(kEvents == sizeof(kEventNames) / sizeof(kEventNames[0]), "one name per event");
 
 static bool (*const kPredicates[])(const CtxState&) = {counts_describe_buffer, moments_continue, planes_current, holds_denoised,
-                                                       holds_temporal, history_held, temporal_of_planes};
+                                                       holds_temporal, history_held, temporal_of_planes, history_has_moments};
 static const char* const kPredicateNames[] = {"counts_describe_buffer", "moments_continue", "planes_current", "holds_denoised",
-                                              "holds_temporal", "history_held", "temporal_of_planes"};
+                                              "holds_temporal", "history_held", "temporal_of_planes", "history_has_moments"};
 constexpr int kPredicateCount = sizeof(kPredicates) / sizeof(kPredicates[0]);
 static_assert(kPredicateCount == sizeof(kPredicateNames) / sizeof(kPredicateNames[0]), "one name per predicate");
 
@@ -87,7 +87,7 @@ struct Fuzz {
     void step()
     {
         const uint64_t stateEpoch = s.stateEpoch, epoch = s.epoch;
-        const bool hist = s.histValid;
+        const bool hist = s.histValid, mom = s.momValid;
         const uint32_t e = next() % (kEvents + 6);       // (a render as likely as four other events)
         if (e < (uint32_t)kEvents) {
             kEventFns[e](s);
@@ -100,6 +100,7 @@ struct Fuzz {
             sky_set(s, held, handle);
             if (held != handle) sh.moved = true;
             check(s.histValid == (hist && held == handle));
+            check(s.momValid == (mom && held == handle));
         } else {
             const unsigned long long cam = next() % 3;
             const RenderStart r = render_begins(s, camera_of(cam));
@@ -110,14 +111,18 @@ struct Fuzz {
         }
         check(!s.adMomValid || s.adCountsValid);
         check((!s.histValid || s.tpValid) && (!s.tpOfPlanes || s.tpValid));
+        check(!s.momValid || s.histValid);
         // the tool's own list of what ends a history and what does not
         if (e < (uint32_t)kEvents) {
             void (*const f)(CtxState&) = kEventFns[e];
             const bool ends = f == scene_or_texture_changed || f == temporal_begins;
             if (f != temporal_done) check(s.histValid == (hist && !ends));
             if (f == features_begin) check(!s.tpOfPlanes);
+            // the moments end with the history (a plain temporal step begins as every step and sets them no more);
+            // only a finished moments step over a held history sets them
+            check(s.momValid == (f == moments_done ? hist : (mom && !ends)));
         } else if (e != (uint32_t)kEvents + 1) {
-            check(s.histValid == hist);              // a sort of the order, a render
+            check(s.histValid == hist && s.momValid == mom);     // a sort of the order, a render
         }
         check(s.stateEpoch >= stateEpoch && s.epoch >= epoch);
         check(s.aheadMisses <= 1000u);
@@ -129,11 +134,11 @@ static void print_state(const CtxState& s, const std::string& extra)
     printf("{\"order\": {\"valid\": %d, \"stale\": %d, \"samples\": %llu, \"strip\": %u}, \"stateEpoch\": %llu, "
            "\"lastState\": %llu, \"launched\": %d, \"lastCam\": %d, \"aheadValid\": %d, \"aheadMisses\": %u, \"adMomValid\": %d, "
            "\"adCountsValid\": %d, \"featValid\": %d, \"dnValid\": %d, \"tpValid\": %d, \"histValid\": %d, "
-           "\"tpOfPlanes\": %d, \"epoch\": %llu%s}\n",
+           "\"tpOfPlanes\": %d, \"momValid\": %d, \"epoch\": %llu%s}\n",
            (int)s.order.valid, (int)s.order.stale, (unsigned long long)s.order.samples, s.order.strip,
            (unsigned long long)s.stateEpoch, (unsigned long long)s.lastState, (int)s.launched, (int)s.lastCam.origin[0],
            (int)s.aheadValid, s.aheadMisses, (int)s.adMomValid, (int)s.adCountsValid, (int)s.featValid, (int)s.dnValid,
-           (int)s.tpValid, (int)s.histValid, (int)s.tpOfPlanes,
+           (int)s.tpValid, (int)s.histValid, (int)s.tpOfPlanes, (int)s.momValid,
            (unsigned long long)s.epoch, extra.c_str());
     fflush(stdout);
 }
