@@ -272,6 +272,12 @@ public:
     const float* temporalVariance();
     void denoiseVariance(const VarianceDenoiseOptions& options);
     void denoiseVariance() { denoiseVariance(VarianceDenoiseOptions()); }
+    // The same filter and the same result, and the output of iteration feedbackLevel - 1 (1..iterations) becomes
+    // the colour of the held history, which the next temporalMoments reprojects (pt_denoise_variance_feedback).
+    // temporalHistory: plane 0..3 of the held history (borrowed, rows x width float4; plane 3 only while the
+    // history has moments).
+    void denoiseVariance(const VarianceDenoiseOptions& options, uint32_t feedbackLevel);
+    const float* temporalHistory(uint32_t plane);
     float getTiming() const;
     uint32_t loadTexture(const char* path);
     void setSkyboxTextureHandle(uint32_t handle);
@@ -308,6 +314,7 @@ private:
     std::vector<float> m_featureBuffer;
     std::vector<float> m_temporalBuffer;
     std::vector<float> m_varianceBuffer;
+    std::vector<float> m_historyBuffer;
     BVH m_bvh;
     void allocHostBuffers();
     void check(int rc, const char* what) const;

@@ -679,6 +679,51 @@ PT_API int pt_denoise_variance_image(int device, uint32_t width, uint32_t height
                                      const float *plane0, const float *plane1, const float *plane2,
                                      const float *variance, const pt_vdenoise_params *params, float *out);
 
+/* ---- The feedback: the filtered colour becomes the history the next frame reprojects ---------------
+ * SVGF's feedback (Schied et al. 2017, section 4.3): the output of an early wavelet level replaces the colour
+ * of the temporal history, so that the filter's noise reduction compounds over frames.  The variance-guided
+ * filter above is unchanged (prepare, iterations between two buffers, finish): the feedback reads an
+ * iteration's output and steers nothing, so the filter's result is word for word pt_denoise_variance's for
+ * the same parameters.  tests/feedback_model.py restates the rule.
+ *
+ * 4. One more parameter, level L with 1 <= L <= iterations.  After iteration index L - 1 (L iterations), for
+ *    every pixel p of the history the last pt_temporal_moments step wrote (h0 = (I, n)):
+ *       T_p = the texel iteration L - 1 wrote for p:  (I'.rgb, v') for a kept pixel, w < 0 otherwise
+ *       fed_p = !(T_p.w < 0) && I'.x finite && I'.y finite && I'.z finite          ("finite": x - x == 0)
+ *       h0_p = fed_p ? (I'.x, I'.y, I'.z, n_p) : h0_p       (a select, then one unconditional 16-byte store)
+ *    n_p is the word that was there; it is never recomputed.  h1, h2, h3 and the variance are not written:
+ *    the moments stay those of the unfiltered signal, so the variance goes on describing the noise of the
+ *    input, not of the filter's output.  The filter's input is the temporal image, not h0: a second call in
+ *    the same frame with the same arguments writes the same words.  I' and h0 are in the same units because
+ *    the DEMODULATE bit must equal the one the moments were made with (pt_denoise_variance's check).  An I'
+ *    that overflowed is not fed back: the pixel keeps its unfiltered history and the next step does not skip
+ *    it.  A pixel that is not kept (a miss, an emissive hit, a variance that is negative or not finite) keeps
+ *    its history too. */
+#define PT_VFEEDBACK_DEFAULT_LEVEL 3
+typedef struct pt_vfeedback_params {
+    uint32_t level;          /* 1..iterations: the iteration whose output is fed back */
+} pt_vfeedback_params;
+/* pt_denoise_variance with the feedback into the held history (the set the last moments step wrote, which
+ * the next step reads).  Allowed exactly where pt_denoise_variance is, with its refusals, and it ends nothing;
+ * in addition PT_ERR_ARG naming `level` unless 1 <= level <= params->iterations, and a null struct is refused.
+ * The result goes where pt_denoise_variance's goes, the same words. */
+PT_API int pt_denoise_variance_feedback(pt_context *ctx, const pt_vdenoise_params *params,
+                                        const pt_vfeedback_params *feedback);
+/* The hipEvent time in ms of the feedback kernel (one float).  PT_ERR_STATE until a feedback call has run on
+ * the held history. */
+PT_API int pt_read_feedback_timing(pt_context *ctx, float *dst);
+/* Plane 0..3 of the held history (rows x width float4): (I, n), (N, id), (P, t), (m1, m2, v, 0).  PT_ERR_STATE
+ * without a held history; PT_ERR_ARG naming `plane` for a plane above 3, or plane 3 of a history without
+ * moments.  What the _image forms take as hist0..3 when a frame is gathered. */
+PT_API int pt_read_temporal_history(pt_context *ctx, uint32_t plane, float *dst);
+/* The same on host arrays, as pt_denoise_variance_image: hist0 (the h0 a pt_temporal_moments_image step
+ * returned) and out_hist0 (the fed h0) are height x width float4.  Errors: pt_last_error(NULL). */
+PT_API int pt_denoise_variance_feedback_image(int device, uint32_t width, uint32_t height, const float *color,
+                                              const float *plane0, const float *plane1, const float *plane2,
+                                              const float *variance, const float *hist0,
+                                              const pt_vdenoise_params *params, const pt_vfeedback_params *feedback,
+                                              float *out, float *out_hist0);
+
 /* ---- Multi-device group (one process, one context per GPU, RCCL over xGMI) -------------------
  * Replaces the reference's hard-coded single device (Pathtracer.cpp:40: cudaSetDevice(0)) behind
  * the same Pathtracer interface: device i renders the row bands b = i, i + N, ... of the image

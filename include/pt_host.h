@@ -105,6 +105,12 @@ PT_API int pth_renderer_temporal_moments(pth_renderer *r, const pt_temporal_para
                                          const pt_variance_params *variance, int reset, int *history_used);
 PT_API const float *pth_renderer_temporal_variance(pth_renderer *r);
 PT_API int pth_renderer_denoise_variance(pth_renderer *r, const pt_vdenoise_params *params);
+/* Pathtracer::denoiseVariance(options, feedbackLevel) / temporalHistory (pt_denoise_variance_feedback,
+ * pt_read_temporal_history, pt_hip.h; single device).  pth_renderer_temporal_history: a borrowed pointer
+ * (rows x width float4) valid until the next call, null on error. */
+PT_API int pth_renderer_denoise_variance_feedback(pth_renderer *r, const pt_vdenoise_params *params,
+                                                  const pt_vfeedback_params *feedback);
+PT_API const float *pth_renderer_temporal_history(pth_renderer *r, uint32_t plane);
 PT_API float pth_renderer_timing(const pth_renderer *r);
 PT_API uint32_t pth_renderer_frames(const pth_renderer *r);
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer *r);

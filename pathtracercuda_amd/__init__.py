@@ -28,7 +28,8 @@ __all__ = ["Pathtracer", "Scene", "make_camera", "camera_rotate", "camera_transl
            "PtBvhNode", "PtHittable", "write_png", "write_hdr", "HITTABLE_TYPES", "MATERIAL_TYPES", "denoise_image",
            "denoise_params", "auto_sigma_color", "denoise_keep_mask", "DENOISE_DEFAULTS", "DENOISE_SIGMA_FACTOR",
            "temporal_params", "temporal_image", "TEMPORAL_DEFAULTS", "variance_params", "vdenoise_params",
-           "temporal_moments_image", "denoise_variance_image", "VARIANCE_DEFAULTS", "VDENOISE_DEFAULTS"]
+           "temporal_moments_image", "denoise_variance_image", "VARIANCE_DEFAULTS", "VDENOISE_DEFAULTS",
+           "vfeedback_params", "denoise_variance_feedback_image", "VFEEDBACK_DEFAULTS"]
 
 HITTABLE_TYPES = ["SPHERE", "CYLINDER", "DISK", "CONE", "PARABOLOID", "QUAD", "CUBE"]   # Hittable.h:9-12
 MATERIAL_TYPES = ["LAMBERT", "GGX", "LAMBERT_GGX"]                                     # Material.h:9-12
@@ -338,6 +339,49 @@ def denoise_variance_image(color, plane0, plane1, plane2, variance, iterations: 
     return out
 
 
+# Default of the feedback of the filtered colour into the history (PT_VFEEDBACK_DEFAULT_LEVEL of
+# include/pt_hip.h).  The feedback itself is off unless asked for (denoise(feedback=L)).
+VFEEDBACK_DEFAULTS = {"level": 3}
+
+
+def vfeedback_params(level: Optional[int] = None, iterations: Optional[int] = None) -> "N.PtVFeedbackParams":
+    """pt_vfeedback_params, refused here (PT_ERR_ARG naming the field) unless 1 <= level <= iterations
+    (iterations=None: the filter's default; the device checks against the parameters it is given)."""
+    level = VFEEDBACK_DEFAULTS["level"] if level is None else level
+    iterations = VDENOISE_DEFAULTS["iterations"] if iterations is None else iterations
+    if isinstance(level, float) and not np.isfinite(level):
+        raise _refuse(f"denoise: feedback level must be 1..iterations, not {level!r}")
+    if int(level) != level or not 1 <= int(level) <= int(iterations):
+        raise _refuse(f"denoise: feedback level must be 1..iterations ({iterations}), not {level!r}")
+    return N.PtVFeedbackParams(int(level))
+
+
+def denoise_variance_feedback_image(color, plane0, plane1, plane2, variance, hist0, level: Optional[int] = None,
+                                    iterations: Optional[int] = None, sigma_l: Optional[float] = None,
+                                    variance_floor: Optional[float] = None, sigma_plane: Optional[float] = None,
+                                    normal_power_log2: Optional[int] = None, demodulate: Optional[bool] = None,
+                                    same_primitive: Optional[bool] = None, staging: int = 0, device: int = 0):
+    """pt_denoise_variance_feedback_image: denoise_variance_image() with the feedback of include/pt_hip.h on host
+    arrays.  `hist0` = the h0 a temporal_moments_image() step returned for the same frame; the output of
+    iteration level - 1 replaces its colours where the pixel is kept and the colour finite.  Returns (out, hist0):
+    out is denoise_variance_image()'s result word for word, hist0 goes into the next step's history."""
+    params = vdenoise_params(iterations, sigma_l, variance_floor, sigma_plane, normal_power_log2, demodulate,
+                             same_primitive, staging)
+    fb = vfeedback_params(level, params.iterations)
+    c = _image4("color", color)
+    planes = [_image4(f"plane{k}", p, c.shape) for k, p in enumerate((plane0, plane1, plane2))]
+    var = _image1("variance", variance, c.shape)
+    h0 = _image4("hist0", hist0, c.shape)
+    out, out_h0 = np.zeros_like(c), np.zeros_like(c)
+    fp = C.POINTER(C.c_float)
+    rc = N.hip().pt_denoise_variance_feedback_image(int(device), c.shape[1], c.shape[0], c.ctypes.data_as(fp),
+                                                    *[p.ctypes.data_as(fp) for p in planes], var.ctypes.data_as(fp),
+                                                    h0.ctypes.data_as(fp), C.byref(params), C.byref(fb),
+                                                    out.ctypes.data_as(fp), out_h0.ctypes.data_as(fp))
+    N.check_ctx(rc, None)
+    return out, out_h0
+
+
 class Scene:
     """A parsed scene file (no GPU): objects in file order, the SAH BVH, camera, textures."""
 
@@ -554,7 +598,7 @@ class Pathtracer:
                 normal_power_log2: Optional[int] = None, demodulate: Optional[bool] = None,
                 same_primitive: Optional[bool] = None, staging: int = 0, frames: Optional[int] = None,
                 source: str = "accumulation", guide: str = "color", sigma_l: Optional[float] = None,
-                variance_floor: Optional[float] = None) -> np.ndarray:
+                variance_floor: Optional[float] = None, feedback: int = 0) -> np.ndarray:
         """Filter the image with the edge-avoiding a-trous denoiser (include/pt_hip.h), guided by the
         planes of the last features(camera) call; returns rows x width x 4 float32 in
         get_hdr_image_data()'s units and leaves the accumulation as it is.  sigma_color=None: a factor times
@@ -565,12 +609,17 @@ class Pathtracer:
         guide="variance" (with source="temporal", after temporal(variance=True)): the colour weight follows the
         per-pixel variance of that step instead of one sigma_color (pt_denoise_variance); sigma_l is in
         standard deviations of the luminance, variance_floor keeps the weight defined where the variance is 0.
+        feedback=L (1..iterations; only with source="temporal", guide="variance"): the same result, and the output
+        of iteration L - 1 becomes the colour of the held history, which the next temporal(variance=True)
+        reprojects (pt_denoise_variance_feedback).  0: no feedback.
         Arguments out of range raise before any device call."""
         self._single("denoise")
         if source not in ("accumulation", "temporal"):
             raise _refuse(f"denoise: source must be 'accumulation' or 'temporal', not {source!r}")
         if guide not in ("color", "variance"):
             raise _refuse(f"denoise: guide must be 'color' or 'variance', not {guide!r}")
+        if feedback != 0 and (source != "temporal" or guide != "variance"):
+            raise _refuse("denoise: feedback needs source='temporal' and guide='variance' (it feeds the temporal history)")
         if guide == "variance":
             if source != "temporal":
                 raise _refuse("denoise: guide='variance' needs source='temporal' (the variance is the temporal history's)")
@@ -578,6 +627,10 @@ class Pathtracer:
                 raise _refuse("denoise: sigma_color is not used with guide='variance' (give sigma_l)")
             vparams = vdenoise_params(iterations, sigma_l, variance_floor, sigma_plane, normal_power_log2, demodulate,
                                       same_primitive, staging)
+            if feedback != 0:
+                fb = vfeedback_params(feedback, vparams.iterations)
+                N.check_ctx(N.hip().pt_denoise_variance_feedback(self._ctx, C.byref(vparams), C.byref(fb)), self._ctx)
+                return self.denoised()
             N.check_ctx(N.hip().pt_denoise_variance(self._ctx, C.byref(vparams)), self._ctx)
             return self.denoised()
         if sigma_l is not None or variance_floor is not None:
@@ -676,6 +729,33 @@ class Pathtracer:
         ms = (C.c_float * 2)()
         N.check_ctx(N.hip().pt_read_temporal_moments_timing(self._ctx, ms), self._ctx)
         return {"step": float(ms[0]), "estimate": float(ms[1])}
+
+    def temporal_history(self):
+        """The held history (pt_read_temporal_history): (h0, h1, h2, h3), rows x width x 4 float32 each -- (I, n),
+        (N, id), (P, t), (m1, m2, v, 0) -- as temporal_moments_image() takes it; h3 is None while the history has
+        no moments.  After denoise(feedback=L) h0 holds the fed colours."""
+        self._single("temporal_history")
+        fp = C.POINTER(C.c_float)
+        planes = []
+        for k in range(3):
+            p = np.zeros((self.rows, self.width, 4), dtype=np.float32)
+            N.check_ctx(N.hip().pt_read_temporal_history(self._ctx, k, p.ctypes.data_as(fp)), self._ctx)
+            planes.append(p)
+        p = np.zeros((self.rows, self.width, 4), dtype=np.float32)
+        rc = N.hip().pt_read_temporal_history(self._ctx, 3, p.ctypes.data_as(fp))
+        if rc == N.PT_ERR_ARG:
+            planes.append(None)
+        else:
+            N.check_ctx(rc, self._ctx)
+            planes.append(p)
+        return tuple(planes)
+
+    def feedback_timing(self) -> float:
+        """Kernel time of the feedback of the last denoise(feedback=L) in ms (hipEvents)."""
+        self._single("feedback_timing")
+        ms = C.c_float(0.0)
+        N.check_ctx(N.hip().pt_read_feedback_timing(self._ctx, C.byref(ms)), self._ctx)
+        return float(ms.value)
 
     def temporal_image(self) -> np.ndarray:
         """The last temporal()'s image again (pt_read_temporal)."""

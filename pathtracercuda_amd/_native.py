@@ -85,6 +85,11 @@ class PtVDenoiseParams(C.Structure):
                 ("staging", C.c_uint32)]
 
 
+class PtVFeedbackParams(C.Structure):
+    """pt_vfeedback_params (pt_hip.h, the feedback of the filtered colour into the temporal history)."""
+    _fields_ = [("level", C.c_uint32)]
+
+
 PT_FEATURE_HIT, PT_FEATURE_EMISSIVE = 1, 2
 PT_TEMPORAL_DEMODULATE, PT_TEMPORAL_SAME_PRIMITIVE = 1, 2
 PT_DENOISE_DEMODULATE, PT_DENOISE_SAME_PRIMITIVE = 1, 2
@@ -169,6 +174,11 @@ _HIP_SYMBOLS = {
                                   + [P(C.c_float)] * 6),
     "pt_denoise_variance_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 5
                                   + [P(PtVDenoiseParams), P(C.c_float)]),
+    "pt_denoise_variance_feedback": (C.c_int, [C.c_void_p, P(PtVDenoiseParams), P(PtVFeedbackParams)]),
+    "pt_read_feedback_timing": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_read_temporal_history": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_float)]),
+    "pt_denoise_variance_feedback_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 6
+                                           + [P(PtVDenoiseParams), P(PtVFeedbackParams), P(C.c_float), P(C.c_float)]),
     "pt_group_create": (C.c_int, [C.c_int, P(C.c_int), C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_void_p)]),
     "pt_group_destroy": (None, [C.c_void_p]),
     "pt_group_size": (C.c_int, [C.c_void_p]),
@@ -221,6 +231,8 @@ _HOST_SYMBOLS = {
     "pth_renderer_temporal_moments": (C.c_int, [C.c_void_p, P(PtTemporalParams), P(PtVarianceParams), C.c_int, P(C.c_int)]),
     "pth_renderer_temporal_variance": (P(C.c_float), [C.c_void_p]),
     "pth_renderer_denoise_variance": (C.c_int, [C.c_void_p, P(PtVDenoiseParams)]),
+    "pth_renderer_denoise_variance_feedback": (C.c_int, [C.c_void_p, P(PtVDenoiseParams), P(PtVFeedbackParams)]),
+    "pth_renderer_temporal_history": (P(C.c_float), [C.c_void_p, C.c_uint32]),
     "pth_renderer_timing": (C.c_float, [C.c_void_p]),
     "pth_renderer_frames": (C.c_uint32, [C.c_void_p]),
     "pth_renderer_local_rows": (C.c_uint32, [C.c_void_p]),

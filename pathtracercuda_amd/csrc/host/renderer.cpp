@@ -254,6 +254,23 @@ void Pathtracer::denoiseVariance(const VarianceDenoiseOptions& o)
     m_denoised = true;
 }
 
+void Pathtracer::denoiseVariance(const VarianceDenoiseOptions& o, uint32_t feedbackLevel)
+{
+    if (m_group) check(PT_ERR_STATE, "denoiseVariance: not available on a device group");
+    const pt_vdenoise_params p = {o.iterations, o.sigmaL, o.varianceFloor, o.sigmaPlane, o.normalPowerLog2, o.flags, o.staging};
+    const pt_vfeedback_params f = {feedbackLevel};
+    check(pt_denoise_variance_feedback(m_ctx, &p, &f), "pt_denoise_variance_feedback");
+    m_denoised = true;
+}
+
+const float* Pathtracer::temporalHistory(uint32_t plane)
+{
+    if (m_group) check(PT_ERR_STATE, "temporalHistory: not available on a device group");
+    m_historyBuffer.resize((size_t)localRows() * m_width * 4);
+    check(pt_read_temporal_history(m_ctx, plane, m_historyBuffer.data()), "pt_read_temporal_history");
+    return m_historyBuffer.data();
+}
+
 float Pathtracer::getTiming() const { return m_timing; }
 
 uint32_t Pathtracer::loadTexture(const char* path)

@@ -1,6 +1,7 @@
 // Per-pixel variance from the temporal history and the variance-guided a-trous filter (pt_temporal_moments,
 // pt_denoise_variance and their _image forms; the rules are written out in include/pt_hip.h and restated in
-// tests/svgf_model.py).  Part of the trace kernel's single translation unit: included by pt_kernels.hip
+// tests/svgf_model.py), and the feedback of the filtered colour into the history (pt_denoise_variance_feedback;
+// tests/feedback_model.py).  Part of the trace kernel's single translation unit: included by pt_kernels.hip
 // inside its anonymous namespace after pt_dev_temporal.h; not a standalone header.
 // Nothing here is used by an existing kernel, and no existing kernel or parameter struct changes.
 #pragma once
@@ -341,4 +342,24 @@ __global__ void __launch_bounds__(256) vdn_finish_kernel(VDenoiseArgs V)
     const f3 D = dn_divisor(A.plane0[i], A.flags);
     const bool keep = !(I.w < 0.0f);
     A.dst[i] = make_float4(keep ? I.x * D.x : c.x, keep ? I.y * D.y : c.y, keep ? I.z * D.z : c.z, 1.0f);
+}
+
+// ---------------------------------------------------------------------------------------------
+// 4. The feedback: the texel iteration L - 1 wrote becomes the colour the next frame reprojects.  Flat, one
+// pixel per lane, two 16 B loads and one unconditional 16 B store; the history length is the word that was
+// there.  A kernel of its own after the iteration, so vdn_iter_kernel's code objects stay what they were.
+// ---------------------------------------------------------------------------------------------
+struct FeedbackArgs {
+    const float4* texel;        // the buffer iteration L - 1 wrote: (I', v') or w < 0
+    float4* h0;                 // the history's (I, n) the last moments step wrote
+    size_t npix;
+};
+
+__global__ void __launch_bounds__(256) vdn_feedback_kernel(FeedbackArgs A)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.npix) return;
+    const float4 T = A.texel[i], h = A.h0[i];
+    const bool fed = !(T.w < 0.0f) && dn_finite(T.x) && dn_finite(T.y) && dn_finite(T.z);
+    A.h0[i] = make_float4(fed ? T.x : h.x, fed ? T.y : h.y, fed ? T.z : h.z, h.w);
 }

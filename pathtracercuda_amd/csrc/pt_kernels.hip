@@ -558,6 +558,9 @@ struct pt_context {
     hipEvent_t tmEv[3] = {};
     float tmMs[2] = {};               // the step, the estimate
     uint32_t tmFlags = 0;             // the flags the held moments were made with
+    hipEvent_t fbEv[2] = {};          // around the feedback kernel (pt_denoise_variance_feedback)
+    float fbMs = 0.0f;
+    bool fbRan = false;               // a feedback call has run since the last moments step
     std::string err;
 };
 
@@ -867,6 +870,8 @@ PT_API void pt_destroy(pt_context* ctx)
     for (auto& e : ctx->dnEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->tmEv)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : ctx->fbEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& t : ctx->hostTex) (void)hipFree((void*)t.texels);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

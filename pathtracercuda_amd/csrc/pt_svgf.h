@@ -1,6 +1,8 @@
 // Entry points of the per-pixel variance and the variance-guided filter (pt_temporal_moments,
 // pt_read_temporal_variance, pt_read_temporal_moments_timing, pt_denoise_variance, pt_temporal_moments_image,
-// pt_denoise_variance_image); the kernels are in pt_dev_svgf.h.  Part of the trace kernel's single
+// pt_denoise_variance_image) and of the feedback of the filtered colour into the history
+// (pt_denoise_variance_feedback, pt_read_feedback_timing, pt_read_temporal_history,
+// pt_denoise_variance_feedback_image); the kernels are in pt_dev_svgf.h.  Part of the trace kernel's single
 // translation unit: included by pt_kernels.hip after pt_temporal.h; not a standalone header.
 #pragma once
 
@@ -88,10 +90,13 @@ static hipError_t moments_run(hipStream_t stream, const pt_temporal_params& p, c
     return hipSuccess;
 }
 
-// denoise_run with the variance: the same buffers and events.
+// denoise_run with the variance: the same buffers and events.  level >= 1 (the feedback, checked by the
+// caller to be <= iterations): the texel iteration level - 1 wrote goes into the history colours fbH0 right
+// after that iteration, between the optional events fbEv[0] and fbEv[1]; the filter reads nothing of fbH0.
 static hipError_t vdenoise_run(hipStream_t stream, const pt_vdenoise_params& p, uint32_t width, uint32_t height,
                                const float4* color, const float4* planes, const float* var, float4* g0, float4* g1,
-                               float4* ping, float4* pong, float4* out, hipEvent_t* ev)
+                               float4* ping, float4* pong, float4* out, hipEvent_t* ev, uint32_t level = 0,
+                               float4* fbH0 = nullptr, hipEvent_t* fbEv = nullptr)
 {
     const size_t npix = (size_t)width * height;
     const unsigned flat = (unsigned)((npix + 255) / 256);
@@ -134,6 +139,13 @@ static hipError_t vdenoise_run(hipStream_t stream, const pt_vdenoise_params& p, 
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (ev && (e = hipEventRecord(ev[2 + i], stream)) != hipSuccess) return e;
+        if (level == i + 1u) {                           // dst is the buffer this iteration wrote, whatever the parity
+            const FeedbackArgs B = {dst, fbH0, npix};
+            if (fbEv && (e = hipEventRecord(fbEv[0], stream)) != hipSuccess) return e;
+            vdn_feedback_kernel<<<flat, 256, 0, stream>>>(B);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            if (fbEv && (e = hipEventRecord(fbEv[1], stream)) != hipSuccess) return e;
+        }
         std::swap(src, dst);
     }
     A.src = src;
@@ -146,6 +158,60 @@ static hipError_t vdenoise_run(hipStream_t stream, const pt_vdenoise_params& p, 
 
 // The context's moments planes (two sets, beside tpBuf's two history sets) and its variance, in one allocation
 static float* moments_variance(pt_context* ctx) { return reinterpret_cast<float*>(ctx->tmBuf + 2 * (size_t)ctx->rows * ctx->width); }
+
+// pt_denoise_variance (level = 0) and pt_denoise_variance_feedback (level >= 1, already checked against
+// params->iterations) on the context; `name` starts every message.
+static int vdenoise_ctx(pt_context* ctx, const pt_vdenoise_params* params, uint32_t level, const char* name)
+{
+    if (!ctx) return PT_ERR_ARG;
+    const std::string who(name);
+    if (const char* why = vdenoise_refusal(params)) return fail(ctx, PT_ERR_ARG, (who + why).c_str());
+    if (!history_has_moments(ctx->st))
+        return fail(ctx, PT_ERR_STATE, (who + "no variance is held (no pt_temporal_moments since the history ended)").c_str());
+    if (!temporal_of_planes(ctx->st))
+        return fail(ctx, PT_ERR_STATE, (who + "pt_render_features has run since the variance was made "
+                                              "(its planes are no longer held)").c_str());
+    if ((params->flags ^ ctx->tmFlags) & PT_DENOISE_DEMODULATE)
+        return fail(ctx, PT_ERR_ARG, (who + "flags: the DEMODULATE bit differs from the one the moments were made with").c_str());
+    // (the whole frame: pt_temporal_moments refuses anything else)
+    PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const size_t npix = (size_t)ctx->rows * ctx->width;
+    denoise_begins(ctx->st);
+    if (!ctx->dnBuf) {
+        PT_HIP_CHECK(ctx, hipMalloc(&ctx->dnBuf, 6 * npix * sizeof(float4)));   // colour, g0, g1, ping, pong, out
+        for (auto& e : ctx->dnEv) PT_HIP_CHECK(ctx, hipEventCreate(&e));
+    }
+    if (level && !ctx->fbEv[0])
+        for (auto& e : ctx->fbEv) PT_HIP_CHECK(ctx, hipEventCreate(&e));
+    // the history set the last moments step wrote: the one the next step reads
+    PT_HIP_CHECK(ctx, vdenoise_run(ctx->stream, *params, ctx->width, ctx->height, ctx->tpBuf + npix, ctx->feat,
+                                   moments_variance(ctx), ctx->dnBuf + npix, ctx->dnBuf + 2 * npix, ctx->dnBuf + 3 * npix,
+                                   ctx->dnBuf + 4 * npix, ctx->dnBuf + 5 * npix, ctx->dnEv, level,
+                                   ctx->tpBuf + (2 + 3 * ctx->tpSet) * npix, level ? ctx->fbEv : nullptr));
+    PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    for (float& m : ctx->dnMs) m = 0.0f;
+    PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[0], ctx->dnEv[0], ctx->dnEv[1]));
+    // what follows the feedback kernel (iteration `level`, or the finish) starts at the feedback's second event
+    for (uint32_t i = 0; i < params->iterations; ++i)
+        PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[1 + i], (level && i == level) ? ctx->fbEv[1] : ctx->dnEv[1 + i],
+                                              ctx->dnEv[2 + i]));
+    PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[9],
+                                          (level == params->iterations) ? ctx->fbEv[1] : ctx->dnEv[1 + params->iterations],
+                                          ctx->dnEv[11]));
+    if (level) {
+        PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->fbMs, ctx->fbEv[0], ctx->fbEv[1]));
+        ctx->fbRan = true;
+    }
+    denoise_done(ctx->st);
+    return PT_OK;
+}
+
+static const char* vfeedback_refusal(const pt_vfeedback_params* f, uint32_t iterations)
+{
+    if (!f) return "feedback params is null";
+    if (!(f->level >= 1u && f->level <= iterations)) return "level must be 1..iterations";
+    return nullptr;
+}
 
 extern "C" {
 
@@ -170,6 +236,7 @@ PT_API int pt_temporal_moments(pt_context* ctx, uint32_t frames, const pt_tempor
         for (auto& e : ctx->tmEv) PT_HIP_CHECK(ctx, hipEventCreate(&e));
     }
     ctx->tpMs = ctx->tmMs[0] = ctx->tmMs[1] = 0.0f;
+    ctx->fbRan = false;                       // the feedback time is of a call on the held history
     const uint32_t from = ctx->tpSet, to = ctx->tpSet ^ 1u;
     if (npix) {
         float4* color = ctx->tpBuf;
@@ -219,34 +286,42 @@ PT_API int pt_read_temporal_moments_timing(pt_context* ctx, float* dst)
 
 PT_API int pt_denoise_variance(pt_context* ctx, const pt_vdenoise_params* params)
 {
+    return vdenoise_ctx(ctx, params, 0, "pt_denoise_variance: ");
+}
+
+PT_API int pt_denoise_variance_feedback(pt_context* ctx, const pt_vdenoise_params* params, const pt_vfeedback_params* feedback)
+{
     if (!ctx) return PT_ERR_ARG;
-    if (const char* why = vdenoise_refusal(params))
-        return fail(ctx, PT_ERR_ARG, (std::string("pt_denoise_variance: ") + why).c_str());
-    if (!history_has_moments(ctx->st))
-        return fail(ctx, PT_ERR_STATE, "pt_denoise_variance: no variance is held (no pt_temporal_moments since the history ended)");
-    if (!temporal_of_planes(ctx->st))
-        return fail(ctx, PT_ERR_STATE, "pt_denoise_variance: pt_render_features has run since the variance was made "
-                                       "(its planes are no longer held)");
-    if ((params->flags ^ ctx->tmFlags) & PT_DENOISE_DEMODULATE)
-        return fail(ctx, PT_ERR_ARG, "pt_denoise_variance: flags: the DEMODULATE bit differs from the one the moments were made with");
-    // (the whole frame: pt_temporal_moments refuses anything else)
+    const char* name = "pt_denoise_variance_feedback: ";
+    if (const char* why = vdenoise_refusal(params)) return fail(ctx, PT_ERR_ARG, (std::string(name) + why).c_str());
+    if (const char* why = vfeedback_refusal(feedback, params->iterations))
+        return fail(ctx, PT_ERR_ARG, (std::string(name) + why).c_str());
+    return vdenoise_ctx(ctx, params, feedback->level, name);
+}
+
+PT_API int pt_read_feedback_timing(pt_context* ctx, float* dst)
+{
+    if (!ctx || !dst) return PT_ERR_ARG;
+    if (!history_has_moments(ctx->st) || !ctx->fbRan)
+        return fail(ctx, PT_ERR_STATE, "pt_read_feedback_timing: no pt_denoise_variance_feedback has run on the held history");
+    *dst = ctx->fbMs;
+    return PT_OK;
+}
+
+PT_API int pt_read_temporal_history(pt_context* ctx, uint32_t plane, float* dst)
+{
+    if (!ctx || !dst) return PT_ERR_ARG;
+    if (!history_held(ctx->st))
+        return fail(ctx, PT_ERR_STATE, "pt_read_temporal_history: no history is held (no pt_temporal since it ended)");
+    if (plane > 3u) return fail(ctx, PT_ERR_ARG, "pt_read_temporal_history: plane must be 0..3");
+    if (plane == 3u && !history_has_moments(ctx->st))
+        return fail(ctx, PT_ERR_ARG, "pt_read_temporal_history: plane 3: the held history has no moments "
+                                     "(no pt_temporal_moments step)");
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const size_t npix = (size_t)ctx->rows * ctx->width;
-    denoise_begins(ctx->st);
-    if (!ctx->dnBuf) {
-        PT_HIP_CHECK(ctx, hipMalloc(&ctx->dnBuf, 6 * npix * sizeof(float4)));   // colour, g0, g1, ping, pong, out
-        for (auto& e : ctx->dnEv) PT_HIP_CHECK(ctx, hipEventCreate(&e));
-    }
-    PT_HIP_CHECK(ctx, vdenoise_run(ctx->stream, *params, ctx->width, ctx->height, ctx->tpBuf + npix, ctx->feat,
-                                   moments_variance(ctx), ctx->dnBuf + npix, ctx->dnBuf + 2 * npix, ctx->dnBuf + 3 * npix,
-                                   ctx->dnBuf + 4 * npix, ctx->dnBuf + 5 * npix, ctx->dnEv));
     PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    for (float& m : ctx->dnMs) m = 0.0f;
-    PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[0], ctx->dnEv[0], ctx->dnEv[1]));
-    for (uint32_t i = 0; i < params->iterations; ++i)
-        PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[1 + i], ctx->dnEv[1 + i], ctx->dnEv[2 + i]));
-    PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->dnMs[9], ctx->dnEv[1 + params->iterations], ctx->dnEv[11]));
-    denoise_done(ctx->st);
+    const size_t npix = (size_t)ctx->rows * ctx->width;
+    const float4* src = plane == 3u ? ctx->tmBuf + ctx->tpSet * npix : ctx->tpBuf + (2 + 3 * ctx->tpSet + plane) * npix;
+    PT_HIP_CHECK(ctx, hipMemcpy(dst, src, npix * sizeof(float4), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -320,6 +395,44 @@ PT_API int pt_denoise_variance_image(int device, uint32_t width, uint32_t height
                          buf + 7 * npix, buf + 8 * npix, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, buf + 8 * npix, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return refuse(PT_ERR_HIP, std::string("HIP error: ") + hipGetErrorString(e));
+    return PT_OK;
+}
+
+PT_API int pt_denoise_variance_feedback_image(int device, uint32_t width, uint32_t height, const float* color,
+                                              const float* plane0, const float* plane1, const float* plane2,
+                                              const float* variance, const float* hist0, const pt_vdenoise_params* params,
+                                              const pt_vfeedback_params* feedback, float* out, float* out_hist0)
+{
+    auto refuse = [](int code, const std::string& msg) {
+        g_freeError = "pt_denoise_variance_feedback_image: " + msg;
+        return code;
+    };
+    if (const char* why = vdenoise_refusal(params)) return refuse(PT_ERR_ARG, why);
+    if (const char* why = vfeedback_refusal(feedback, params->iterations)) return refuse(PT_ERR_ARG, why);
+    if (!color || !plane0 || !plane1 || !plane2 || !variance || !out) return refuse(PT_ERR_ARG, "an array is null");
+    if (!hist0 || !out_hist0) return refuse(PT_ERR_ARG, "hist0 or out_hist0 is null");
+    if (width == 0 || height == 0 || (uint64_t)width * height >= (1ull << 30) || height > 8u * 0xffffu)
+        return refuse(PT_ERR_ARG, "width x height must be 1 .. 2^30 - 1 pixels, height at most 524280");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return refuse(PT_ERR_NO_DEVICE, "no GPU visible");
+    if (device < 0 || device >= n) return refuse(PT_ERR_ARG, "device out of range");
+    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
+    float4* buf = nullptr;                  // colour, 3 planes, g0, g1, ping, pong, out, hist0, the variance
+    const float* in[4] = {color, plane0, plane1, plane2};
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc(&buf, 10 * bytes + npix * sizeof(float));
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipMemcpy(buf + k * npix, in[k], bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + 9 * npix, hist0, bytes, hipMemcpyHostToDevice);
+    float* var = reinterpret_cast<float*>(buf + 10 * npix);
+    if (e == hipSuccess) e = hipMemcpy(var, variance, npix * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = vdenoise_run(nullptr, *params, width, height, buf, buf + npix, var, buf + 4 * npix, buf + 5 * npix, buf + 6 * npix,
+                         buf + 7 * npix, buf + 8 * npix, nullptr, feedback->level, buf + 9 * npix, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, buf + 8 * npix, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_hist0, buf + 9 * npix, bytes, hipMemcpyDeviceToHost);
     (void)hipFree(buf);
     if (e != hipSuccess) return refuse(PT_ERR_HIP, std::string("HIP error: ") + hipGetErrorString(e));
     return PT_OK;
