@@ -278,6 +278,26 @@ public:
     // history has moments).
     void denoiseVariance(const VarianceDenoiseOptions& options, uint32_t feedbackLevel);
     const float* temporalHistory(uint32_t plane);
+    // The same filter after renderAdaptive and renderFeatures, its variance made from the adaptive render's own
+    // per-pixel moments (pt_denoise_adaptive, rule 5 of pt_hip.h): a pixel with fewer than minBatches calls takes
+    // the larger of its own batch-means estimate and the spread of its 7 x 7 same-surface window.  The result is a
+    // denoised image, as denoiseVariance's; the DEMODULATE bits of the two option sets must agree.
+    // adaptiveVariance: that variance (borrowed, rows x width floats, -1 where the rule gives none), until a render
+    // writes the accumulation or renderFeatures runs.  Single device only.
+    struct AdaptiveVarianceOptions {
+        uint32_t minBatches = PT_AVARIANCE_DEFAULT_MIN_BATCHES;
+        float sigmaPlane = PT_AVARIANCE_DEFAULT_SIGMA_PLANE;
+        float normalCosMin = PT_AVARIANCE_DEFAULT_NORMAL_COS_MIN;
+        uint32_t flags = PT_AVARIANCE_DEFAULT_FLAGS;
+    };
+    void denoiseAdaptive(const AdaptiveVarianceOptions& variance, const VarianceDenoiseOptions& options);
+    void denoiseAdaptive()
+    {
+        VarianceDenoiseOptions options;
+        options.sigmaL = PT_ADENOISE_DEFAULT_SIGMA_L;      // this source's sweep chose another sigma_l than the temporal one's
+        denoiseAdaptive(AdaptiveVarianceOptions(), options);
+    }
+    const float* adaptiveVariance();
     float getTiming() const;
     uint32_t loadTexture(const char* path);
     void setSkyboxTextureHandle(uint32_t handle);
@@ -338,6 +358,7 @@ struct Params {
     float m_adaptive = -1.0f;        // CLI -adaptive <tolerance>: >= 0 renders adaptively, m_spp is the budget
     unsigned int m_minSpp = 0;       // CLI -minspp: samples every pixel gets (0 = two calls)
     unsigned int m_denoise = 0;      // CLI -denoise [N]: a-trous iterations applied before the image is written (0 = off)
+    bool m_denoiseAdaptive = false;  // CLI -denoise_guide adaptive: the filter follows the adaptive render's own variance
 };
 
 Camera loadScene(Pathtracer& pathtracer, const Params& params);

@@ -724,6 +724,87 @@ PT_API int pt_denoise_variance_feedback_image(int device, uint32_t width, uint32
                                               const pt_vdenoise_params *params, const pt_vfeedback_params *feedback,
                                               float *out, float *out_hist0);
 
+/* ---- The variance of an adaptive render's image, and the filter guided by it ------------------------
+ * pt_render_adaptive keeps, per pixel, m1 = sum y, m2 = sum y^2 and n, y being the luminance of each call's
+ * colour sum: what an error estimate is made of.  Rule 5 turns them into the per-pixel variance that rule 3
+ * (the variance-guided filter above) takes, so that one adaptively rendered still image can be filtered with a
+ * per-pixel colour weight and without a temporal history.  All float32, no contraction, + - x /, compares and
+ * selects only; lum, clamp0 and "finite" as above.  tests/adaptive_variance_model.py restates the rule.
+ *
+ * 5. The variance of an adaptive render's image.  Per pixel p: the colour C_p = accum_p / (float)max(n_p, 1)
+ *    (the image pt_denoise filters after an adaptive render), the feature planes of the last
+ *    pt_render_features (A, id; N, t; P, flags), and m1_p, m2_p, n_p.  Parameters: pt_adaptive_variance_params.
+ *     D_p = pt_denoise's: per channel  A > 1/64 ? A : 1/64  when DEMODULATE, else 1;   I_p = C_p / D_p
+ *     l_p = lum(I_p);   g_p = DEMODULATE ? lum(D_p) : 1
+ *     ok_p = HIT && !EMISSIVE && l_p finite && every component of N_p, P_p finite
+ *     !ok_p, or n_p < 2, or m1_p or m2_p not finite:  var_p = -1
+ *     otherwise the batch-means variance of the mean, in adapt_flag_kernel's operations up to se2 (the
+ *     convergence rule of pt_render_adaptive forms the same words):
+ *         k = (float)n;  mean = m1 / k;  ss = m2 - m1 * mean;  if (ss < 0) ss = 0;  se2 = ss / (k * (k - 1))
+ *         own = clamp0(se2 / (g_p * g_p))
+ *       The units match with no spp in the rule: y is the luminance of a call's sum and C the accumulation
+ *       over n, so se2 is the variance of lum(C_p).  Dividing by lum(D)^2 takes it to the variance of l_p
+ *       exactly for a grey albedo (D.x = D.y = D.z) and approximately otherwise: lum(C / D) is not
+ *       lum(C) / lum(D) when the channels of D differ.
+ *     n_p >= min_batches:  var_p = own
+ *     otherwise (a young pixel) the 7 x 7 same-surface window of rule 2 at unit spacing:
+ *       k = 0, s1 = 0, s2 = 0;  m = sigma_plane * t_p;  mm = m * m
+ *       for dy = -3 .. 3 (outer), dx = -3 .. 3 (inner), q = p + (dx, dy):
+ *       the centre tap always counts; any other tap is skipped (by a select; its index is clamped into the
+ *       image before the load) when q is outside the image, or !ok_q, or N_p . N_q < normal_cos_min, or with
+ *       g = N_p . (P_q - P_p)  !(g*g <= mm), or SAME_PRIMITIVE is set and id_q != id_p;  otherwise
+ *         k = k + 1;  s1 = s1 + l_q;  s2 = s2 + l_q * l_q
+ *       mean = s1 / k;  vs = clamp0(s2 / k - mean * mean);  var_p = vs > own ? vs : own
+ *     The maximum is what the window is for.  A pixel whose few calls all returned the same value (the
+ *     zero-variance dark pixel of a noisy neighbourhood) has own = 0 exactly; with den = variance_floor alone
+ *     rule 3's colour weight would shut out every neighbour and leave it as a speck.  The spread of its
+ *     same-surface neighbourhood is the evidence that it is not converged.
+ *    Accepted: min_batches 2..255, sigma_plane >= 1e-6 and finite, normal_cos_min -1..1, flags within
+ *    PT_DENOISE_DEMODULATE | PT_DENOISE_SAME_PRIMITIVE; anything else (a NaN included) is PT_ERR_ARG and the
+ *    message names the field.
+ *    The filter is rule 3 unchanged, with color = C and var = this rule's output; its DEMODULATE bit must be
+ *    this rule's. */
+/* Defaults of the layers above (C++ Pathtracer::denoiseAdaptive, Python); sigma_plane, normal_cos_min and flags
+ * are the shipped values of rule 2 (PT_TEMPORAL_DEFAULT_*).  min_batches and the filter's sigma_l for this source
+ * are the minimiser of the sweep of tools/adaptive_variance_probe.py (profiles/adaptive_variance_probe.json,
+ * DESIGN.md 5.12); the filter's other defaults are PT_VDENOISE_DEFAULT_*. */
+#define PT_AVARIANCE_DEFAULT_MIN_BATCHES 32
+#define PT_ADENOISE_DEFAULT_SIGMA_L 2.0f
+#define PT_AVARIANCE_DEFAULT_SIGMA_PLANE 0.3f
+#define PT_AVARIANCE_DEFAULT_NORMAL_COS_MIN 0.0f
+#define PT_AVARIANCE_DEFAULT_FLAGS 1u
+typedef struct pt_adaptive_variance_params {
+    uint32_t min_batches;    /* calls from which a pixel's own batch-means estimate is trusted */
+    float sigma_plane;       /* relative to the hit distance */
+    float normal_cos_min;
+    uint32_t flags;          /* PT_DENOISE_DEMODULATE, PT_DENOISE_SAME_PRIMITIVE */
+} pt_adaptive_variance_params;
+
+/* Rule 5 on the context's adaptive render and planes, then rule 3 with that variance: the colour (per-pixel
+ * division, as pt_denoise after an adaptive render), the estimate, the filter.  The result goes where
+ * pt_denoise's goes (pt_read_denoised, pt_tonemap_denoised, pt_read_denoise_timing).  params->staging selects
+ * the form of the estimate kernel as it does the filter's (0 automatic, 1 staged in LDS, 2 unstaged).  The
+ * accumulation, RNG, moments, counts, tile costs and run-ahead stash are not written.  PT_ERR_STATE, naming the
+ * reason, unless an adaptive render describes the buffer and the feature planes are current; PT_ERR_ARG on a
+ * band partition and when the DEMODULATE bits of the two parameter sets differ.  A refused call changes nothing.
+ * "The held variance is of the counts" from the end of this call until a launch writes the accumulation (a
+ * render, the next adaptive render) or pt_render_features begins. */
+PT_API int pt_denoise_adaptive(pt_context *ctx, const pt_adaptive_variance_params *variance,
+                               const pt_vdenoise_params *params);
+/* The variance of the last pt_denoise_adaptive (rows x width float; -1 where rule 5 gives none) and the
+ * hipEvent time in ms of its adaptive_variance_kernel (one float; the per-pixel pass before it is not in it).
+ * PT_ERR_STATE unless the held variance is of the counts. */
+PT_API int pt_read_adaptive_variance(pt_context *ctx, float *dst);
+PT_API int pt_read_adaptive_variance_timing(pt_context *ctx, float *dst);
+/* Rule 5 on host arrays, without a context (as pt_denoise_variance_image), for a gathered frame: color and the
+ * planes are height x width float4, moments is height x width x 3 as pt_read_moments returns it (m1, m2, n as
+ * uint32 bits), out_variance height x width float.  staging 0..2 as above.  The filter on host arrays is
+ * pt_denoise_variance_image.  Errors: pt_last_error(NULL). */
+PT_API int pt_adaptive_variance_image(int device, uint32_t width, uint32_t height, const float *color,
+                                      const float *plane0, const float *plane1, const float *plane2,
+                                      const float *moments, const pt_adaptive_variance_params *params,
+                                      uint32_t staging, float *out_variance);
+
 /* ---- Multi-device group (one process, one context per GPU, RCCL over xGMI) -------------------
  * Replaces the reference's hard-coded single device (Pathtracer.cpp:40: cudaSetDevice(0)) behind
  * the same Pathtracer interface: device i renders the row bands b = i, i + N, ... of the image

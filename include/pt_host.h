@@ -111,6 +111,13 @@ PT_API int pth_renderer_denoise_variance(pth_renderer *r, const pt_vdenoise_para
 PT_API int pth_renderer_denoise_variance_feedback(pth_renderer *r, const pt_vdenoise_params *params,
                                                   const pt_vfeedback_params *feedback);
 PT_API const float *pth_renderer_temporal_history(pth_renderer *r, uint32_t plane);
+/* Pathtracer::denoiseAdaptive / adaptiveVariance (pt_denoise_adaptive, pt_read_adaptive_variance, pt_hip.h; single
+ * device).  After pth_renderer_denoise_adaptive the image calls return the filtered image, as after
+ * pth_renderer_denoise_variance.  pth_renderer_adaptive_variance: a borrowed pointer (rows x width floats) valid
+ * until the next call, null on error. */
+PT_API int pth_renderer_denoise_adaptive(pth_renderer *r, const pt_adaptive_variance_params *variance,
+                                         const pt_vdenoise_params *params);
+PT_API const float *pth_renderer_adaptive_variance(pth_renderer *r);
 PT_API float pth_renderer_timing(const pth_renderer *r);
 PT_API uint32_t pth_renderer_frames(const pth_renderer *r);
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer *r);

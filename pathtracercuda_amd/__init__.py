@@ -29,7 +29,8 @@ __all__ = ["Pathtracer", "Scene", "make_camera", "camera_rotate", "camera_transl
            "denoise_params", "auto_sigma_color", "denoise_keep_mask", "DENOISE_DEFAULTS", "DENOISE_SIGMA_FACTOR",
            "temporal_params", "temporal_image", "TEMPORAL_DEFAULTS", "variance_params", "vdenoise_params",
            "temporal_moments_image", "denoise_variance_image", "VARIANCE_DEFAULTS", "VDENOISE_DEFAULTS",
-           "vfeedback_params", "denoise_variance_feedback_image", "VFEEDBACK_DEFAULTS"]
+           "vfeedback_params", "denoise_variance_feedback_image", "VFEEDBACK_DEFAULTS", "adaptive_variance_params",
+           "adaptive_variance_image", "AVARIANCE_DEFAULTS", "ADENOISE_SIGMA_L"]
 
 HITTABLE_TYPES = ["SPHERE", "CYLINDER", "DISK", "CONE", "PARABOLOID", "QUAD", "CUBE"]   # Hittable.h:9-12
 MATERIAL_TYPES = ["LAMBERT", "GGX", "LAMBERT_GGX"]                                     # Material.h:9-12
@@ -382,6 +383,66 @@ def denoise_variance_feedback_image(color, plane0, plane1, plane2, variance, his
     return out, out_h0
 
 
+# Defaults of the variance of an adaptive render's image (PT_AVARIANCE_DEFAULT_* of include/pt_hip.h; DESIGN.md
+# §5.12): sigma_plane, normal_cos_min and the flags are the temporal pass's, whose same-surface window this is.
+# min_batches and ADENOISE_SIGMA_L, the filter's sigma_l for this source, are the minimiser of the sweep of
+# tools/adaptive_variance_probe.py (profiles/adaptive_variance_probe.json); the filter's other defaults are
+# VDENOISE_DEFAULTS.
+ADENOISE_SIGMA_L = 2.0
+AVARIANCE_DEFAULTS = {"min_batches": 32, "sigma_plane": 0.3, "normal_cos_min": 0.0, "demodulate": True,
+                      "same_primitive": False}
+
+
+def adaptive_variance_params(min_batches: Optional[int] = None, sigma_plane: Optional[float] = None,
+                             normal_cos_min: Optional[float] = None, demodulate: Optional[bool] = None,
+                             same_primitive: Optional[bool] = None) -> "N.PtAdaptiveVarianceParams":
+    """pt_adaptive_variance_params from keyword arguments, refused here (PT_ERR_ARG naming the field) before any
+    device call when a value is outside the accepted range of include/pt_hip.h."""
+    d = AVARIANCE_DEFAULTS
+    min_batches = d["min_batches"] if min_batches is None else min_batches
+    sigma_plane = d["sigma_plane"] if sigma_plane is None else sigma_plane
+    normal_cos_min = d["normal_cos_min"] if normal_cos_min is None else normal_cos_min
+    demodulate = d["demodulate"] if demodulate is None else demodulate
+    same_primitive = d["same_primitive"] if same_primitive is None else same_primitive
+    if isinstance(min_batches, float) and not np.isfinite(min_batches):
+        raise _refuse(f"denoise: min_batches must be 2..255, not {min_batches!r}")
+    if int(min_batches) != min_batches or not 2 <= int(min_batches) <= 255:
+        raise _refuse(f"denoise: min_batches must be 2..255, not {min_batches!r}")
+    sp, nc = np.float32(sigma_plane), np.float32(normal_cos_min)
+    if not (sp >= np.float32(1e-6) and np.isfinite(sp)):
+        raise _refuse(f"denoise: variance sigma_plane must be >= 1e-6 and finite, not {sigma_plane!r}")
+    if not -1 <= nc <= 1:
+        raise _refuse(f"denoise: normal_cos_min must be -1..1, not {normal_cos_min!r}")
+    flags = (N.PT_DENOISE_DEMODULATE if demodulate else 0) | (N.PT_DENOISE_SAME_PRIMITIVE if same_primitive else 0)
+    return N.PtAdaptiveVarianceParams(int(min_batches), float(sp), float(nc), flags)
+
+
+def adaptive_variance_image(color, plane0, plane1, plane2, moments, min_batches: Optional[int] = None,
+                            sigma_plane: Optional[float] = None, normal_cos_min: Optional[float] = None,
+                            demodulate: Optional[bool] = None, same_primitive: Optional[bool] = None, staging: int = 0,
+                            device: int = 0) -> np.ndarray:
+    """pt_adaptive_variance_image: the variance of an adaptive render's image (rule 5 of include/pt_hip.h) on host
+    arrays, without a Pathtracer -- for a frame gathered from several GPUs.  `color` is the accumulation divided by
+    every pixel's own count (get_hdr_image_data() after render_adaptive), the planes are features()["planes"],
+    `moments` is Pathtracer.moments() (height x width x 3).  Returns height x width float32, -1 where the rule
+    gives none; denoise_variance_image() takes it."""
+    params = adaptive_variance_params(min_batches, sigma_plane, normal_cos_min, demodulate, same_primitive)
+    if staging not in (0, 1, 2):
+        raise _refuse(f"denoise: staging must be 0, 1 or 2, not {staging!r}")
+    c = _image4("color", color)
+    planes = [_image4(f"plane{k}", p, c.shape) for k, p in enumerate((plane0, plane1, plane2))]
+    mom = np.ascontiguousarray(moments, dtype=np.float32)
+    if mom.shape != c.shape[:2] + (3,):
+        raise _refuse(f"adaptive_variance_image: moments has shape {mom.shape}, color has {c.shape}")
+    out = np.zeros(c.shape[:2], dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    rc = N.hip().pt_adaptive_variance_image(int(device), c.shape[1], c.shape[0], c.ctypes.data_as(fp),
+                                            *[p.ctypes.data_as(fp) for p in planes], mom.ctypes.data_as(fp),
+                                            C.byref(params), int(staging), out.ctypes.data_as(fp))
+    N.check_ctx(rc, None)
+    return out
+
+
 class Scene:
     """A parsed scene file (no GPU): objects in file order, the SAH BVH, camera, textures."""
 
@@ -598,7 +659,8 @@ class Pathtracer:
                 normal_power_log2: Optional[int] = None, demodulate: Optional[bool] = None,
                 same_primitive: Optional[bool] = None, staging: int = 0, frames: Optional[int] = None,
                 source: str = "accumulation", guide: str = "color", sigma_l: Optional[float] = None,
-                variance_floor: Optional[float] = None, feedback: int = 0) -> np.ndarray:
+                variance_floor: Optional[float] = None, feedback: int = 0, min_batches: Optional[int] = None,
+                normal_cos_min: Optional[float] = None, window_sigma_plane: Optional[float] = None) -> np.ndarray:
         """Filter the image with the edge-avoiding a-trous denoiser (include/pt_hip.h), guided by the
         planes of the last features(camera) call; returns rows x width x 4 float32 in
         get_hdr_image_data()'s units and leaves the accumulation as it is.  sigma_color=None: a factor times
@@ -612,12 +674,36 @@ class Pathtracer:
         feedback=L (1..iterations; only with source="temporal", guide="variance"): the same result, and the output
         of iteration L - 1 becomes the colour of the held history, which the next temporal(variance=True)
         reprojects (pt_denoise_variance_feedback).  0: no feedback.
+        guide="adaptive" (with source="accumulation", after render_adaptive and features): the same filter, its
+        variance made from the adaptive render's own per-pixel moments (pt_denoise_adaptive; adaptive_variance()
+        returns it).  A pixel with fewer than `min_batches` calls takes the larger of its own estimate and the
+        spread of its 7 x 7 same-surface window, whose plane and normal tests take `window_sigma_plane` and
+        `normal_cos_min`; sigma_l (default ADENOISE_SIGMA_L), variance_floor and the rest are the filter's as with
+        guide="variance".
         Arguments out of range raise before any device call."""
         self._single("denoise")
         if source not in ("accumulation", "temporal"):
             raise _refuse(f"denoise: source must be 'accumulation' or 'temporal', not {source!r}")
-        if guide not in ("color", "variance"):
-            raise _refuse(f"denoise: guide must be 'color' or 'variance', not {guide!r}")
+        if guide not in ("color", "variance", "adaptive"):
+            raise _refuse(f"denoise: guide must be 'color', 'variance' or 'adaptive', not {guide!r}")
+        if guide == "adaptive":
+            if source != "accumulation":
+                raise _refuse("denoise: guide='adaptive' needs source='accumulation' (the variance is of the adaptive "
+                              "render's own moments)")
+            if sigma_color is not None:
+                raise _refuse("denoise: sigma_color is not used with guide='adaptive' (give sigma_l)")
+            if feedback != 0:
+                raise _refuse("denoise: feedback is not used with guide='adaptive' (there is no temporal history to feed)")
+            if frames is not None:
+                raise _refuse("denoise: frames is not used with guide='adaptive' (every pixel is divided by its own count)")
+            vparams = vdenoise_params(iterations, ADENOISE_SIGMA_L if sigma_l is None else sigma_l, variance_floor,
+                                      sigma_plane, normal_power_log2, demodulate, same_primitive, staging)
+            aparams = adaptive_variance_params(min_batches, window_sigma_plane, normal_cos_min,
+                                               bool(vparams.flags & N.PT_DENOISE_DEMODULATE), same_primitive)
+            N.check_ctx(N.hip().pt_denoise_adaptive(self._ctx, C.byref(aparams), C.byref(vparams)), self._ctx)
+            return self.denoised()
+        if min_batches is not None or normal_cos_min is not None or window_sigma_plane is not None:
+            raise _refuse("denoise: min_batches, normal_cos_min and window_sigma_plane are given without guide='adaptive'")
         if feedback != 0 and (source != "temporal" or guide != "variance"):
             raise _refuse("denoise: feedback needs source='temporal' and guide='variance' (it feeds the temporal history)")
         if guide == "variance":
@@ -659,6 +745,22 @@ class Pathtracer:
             params.sigma_color = auto_sigma_color(color, *planes, demodulate=demod)
         N.check_ctx(N.hip().pt_denoise(self._ctx, f, C.byref(params)), self._ctx)
         return self.denoised()
+
+    def adaptive_variance(self) -> np.ndarray:
+        """The per-pixel variance the last denoise(guide="adaptive") made (pt_read_adaptive_variance): rows x width
+        float32, of the luminance of the (demodulated) colour; -1 where the pixel is not a finite, non-emissive
+        hit or has fewer than two calls.  Held until a render writes the accumulation or features() runs."""
+        self._single("adaptive_variance")
+        out = np.zeros((self.rows, self.width), dtype=np.float32)
+        N.check_ctx(N.hip().pt_read_adaptive_variance(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float))), self._ctx)
+        return out
+
+    def adaptive_variance_timing(self) -> float:
+        """Kernel time of the window estimate of the last denoise(guide="adaptive") in ms (hipEvents)."""
+        self._single("adaptive_variance_timing")
+        ms = C.c_float(0.0)
+        N.check_ctx(N.hip().pt_read_adaptive_variance_timing(self._ctx, C.byref(ms)), self._ctx)
+        return float(ms.value)
 
     def denoised(self) -> np.ndarray:
         """The last denoise()'s result again (pt_read_denoised)."""

@@ -90,6 +90,12 @@ class PtVFeedbackParams(C.Structure):
     _fields_ = [("level", C.c_uint32)]
 
 
+class PtAdaptiveVarianceParams(C.Structure):
+    """pt_adaptive_variance_params (pt_hip.h, the variance of an adaptive render's image)."""
+    _fields_ = [("min_batches", C.c_uint32), ("sigma_plane", C.c_float), ("normal_cos_min", C.c_float),
+                ("flags", C.c_uint32)]
+
+
 PT_FEATURE_HIT, PT_FEATURE_EMISSIVE = 1, 2
 PT_TEMPORAL_DEMODULATE, PT_TEMPORAL_SAME_PRIMITIVE = 1, 2
 PT_DENOISE_DEMODULATE, PT_DENOISE_SAME_PRIMITIVE = 1, 2
@@ -179,6 +185,11 @@ _HIP_SYMBOLS = {
     "pt_read_temporal_history": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_float)]),
     "pt_denoise_variance_feedback_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 6
                                            + [P(PtVDenoiseParams), P(PtVFeedbackParams), P(C.c_float), P(C.c_float)]),
+    "pt_denoise_adaptive": (C.c_int, [C.c_void_p, P(PtAdaptiveVarianceParams), P(PtVDenoiseParams)]),
+    "pt_read_adaptive_variance": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_read_adaptive_variance_timing": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_adaptive_variance_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 5
+                                   + [P(PtAdaptiveVarianceParams), C.c_uint32, P(C.c_float)]),
     "pt_group_create": (C.c_int, [C.c_int, P(C.c_int), C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_void_p)]),
     "pt_group_destroy": (None, [C.c_void_p]),
     "pt_group_size": (C.c_int, [C.c_void_p]),
@@ -233,6 +244,8 @@ _HOST_SYMBOLS = {
     "pth_renderer_denoise_variance": (C.c_int, [C.c_void_p, P(PtVDenoiseParams)]),
     "pth_renderer_denoise_variance_feedback": (C.c_int, [C.c_void_p, P(PtVDenoiseParams), P(PtVFeedbackParams)]),
     "pth_renderer_temporal_history": (P(C.c_float), [C.c_void_p, C.c_uint32]),
+    "pth_renderer_denoise_adaptive": (C.c_int, [C.c_void_p, P(PtAdaptiveVarianceParams), P(PtVDenoiseParams)]),
+    "pth_renderer_adaptive_variance": (P(C.c_float), [C.c_void_p]),
     "pth_renderer_timing": (C.c_float, [C.c_void_p]),
     "pth_renderer_frames": (C.c_uint32, [C.c_void_p]),
     "pth_renderer_local_rows": (C.c_uint32, [C.c_void_p]),

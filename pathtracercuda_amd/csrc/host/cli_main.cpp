@@ -13,6 +13,10 @@
 //   -denoise [N]   filter the image before -o / -ohdr write it: the edge-avoiding a-trous denoiser guided
 //                  by the first-hit feature buffers (Pathtracer::renderFeatures + denoise), N = 1..8
 //                  iterations (default 5), the other parameters at their defaults.  One GPU.
+//   -denoise_guide adaptive
+//                  with -adaptive and -denoise: the filter's colour weight follows a per-pixel variance made from
+//                  the adaptive render's own moments (Pathtracer::denoiseAdaptive) instead of one colour sigma
+//                  for the image.  Without both of them the option is invalid.
 // The windowed / interactive mode (-window, -enable_controls) is not supported.
 #include <algorithm>
 #include <cstdio>
@@ -93,10 +97,20 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
             } else ++i;
             continue;
         }
+        if (strcmp(argv[i], "-denoise_guide") == 0) {
+            if (i + 1 < argc && strcmp(argv[i + 1], "adaptive") == 0) params.m_denoiseAdaptive = true;
+            else { printf("Invalid input for -denoise_guide!\n"); displayHelp = true; }
+            i += 2;
+            continue;
+        }
         if (strcmp(argv[i], "-minspp") == 0) { uintArg(i, "-minspp", params.m_minSpp); i += 2; continue; }
         printf("Can't parse argument: %s\n", argv[i]);
         displayHelp = true;
         break;
+    }
+    if (params.m_denoiseAdaptive && !(params.m_adaptive >= 0.0f && params.m_denoise)) {
+        printf("Invalid input for -denoise_guide! (adaptive needs both -adaptive and -denoise)\n");
+        displayHelp = true;
     }
     // (`pathtracer -help` alone lists the options: the lone argument is not an input file)
     const bool helpOnly = argc == 2 && strcmp(argv[1], helpOption) == 0;
@@ -124,6 +138,8 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
         printf("%-30s Samples every pixel gets with -adaptive (default two calls)\n", "-minspp");
         printf("%-30s Denoise before writing: a-trous filter guided by first-hit features, N = 1..8 iterations (default 5)\n",
                "-denoise [N]");
+        printf("%-30s With -adaptive and -denoise: guide the filter by the adaptive render's own per-pixel variance\n",
+               "-denoise_guide adaptive");
         return false;
     }
     params.m_enableControls = params.m_enableControls && params.m_showWindow;
@@ -207,7 +223,14 @@ int main(int argc, char* argv[])
     }
     if (!adaptive) printf("Finished accumulating %d samples in %f ms GPU time\n", (int)params.m_spp, totalGpuTime);
 
-    if (params.m_denoise) {
+    if (params.m_denoise && params.m_denoiseAdaptive) {
+        Pathtracer::VarianceDenoiseOptions options;
+        options.iterations = params.m_denoise;
+        options.sigmaL = PT_ADENOISE_DEFAULT_SIGMA_L;
+        pathtracer->renderFeatures(camera);
+        pathtracer->denoiseAdaptive(Pathtracer::AdaptiveVarianceOptions(), options);
+        printf("Denoised: %u a-trous iterations, guided by the adaptive render's variance\n", options.iterations);
+    } else if (params.m_denoise) {
         Pathtracer::DenoiseOptions options;
         options.iterations = params.m_denoise;
         pathtracer->renderFeatures(camera);

@@ -430,6 +430,37 @@ PT_API const float* pth_renderer_temporal_history(pth_renderer* r, uint32_t plan
     return nullptr;
 }
 
+PT_API int pth_renderer_denoise_adaptive(pth_renderer* r, const pt_adaptive_variance_params* variance,
+                                         const pt_vdenoise_params* params)
+{
+    if (!r || !variance || !params) return setError(PT_ERR_ARG, "invalid argument");
+    PTH_GUARD_BEGIN
+    Pathtracer::AdaptiveVarianceOptions a;
+    a.minBatches = variance->min_batches;
+    a.sigmaPlane = variance->sigma_plane;
+    a.normalCosMin = variance->normal_cos_min;
+    a.flags = variance->flags;
+    Pathtracer::VarianceDenoiseOptions o;
+    o.iterations = params->iterations;
+    o.sigmaL = params->sigma_l;
+    o.varianceFloor = params->variance_floor;
+    o.sigmaPlane = params->sigma_plane;
+    o.normalPowerLog2 = params->normal_power_log2;
+    o.flags = params->flags;
+    o.staging = params->staging;
+    r->pt->denoiseAdaptive(a, o);
+    return PT_OK;
+    PTH_GUARD_END
+}
+
+PT_API const float* pth_renderer_adaptive_variance(pth_renderer* r)
+{
+    if (!r) return nullptr;
+    ptamd::g_throwOnError = true;
+    try { return r->pt->adaptiveVariance(); } catch (const std::exception& e) { setError(PT_ERR_STATE, e.what()); }
+    return nullptr;
+}
+
 PT_API float pth_renderer_timing(const pth_renderer* r) { return r ? r->pt->getTiming() : 0.0f; }
 PT_API uint32_t pth_renderer_frames(const pth_renderer* r) { return r ? r->pt->accumulatedFrames() : 0; }
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer* r) { return r ? r->pt->localRows() : 0; }

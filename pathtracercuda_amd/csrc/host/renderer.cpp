@@ -263,6 +263,23 @@ void Pathtracer::denoiseVariance(const VarianceDenoiseOptions& o, uint32_t feedb
     m_denoised = true;
 }
 
+void Pathtracer::denoiseAdaptive(const AdaptiveVarianceOptions& a, const VarianceDenoiseOptions& o)
+{
+    if (m_group) check(PT_ERR_STATE, "denoiseAdaptive: not available on a device group");
+    const pt_adaptive_variance_params v = {a.minBatches, a.sigmaPlane, a.normalCosMin, a.flags};
+    const pt_vdenoise_params p = {o.iterations, o.sigmaL, o.varianceFloor, o.sigmaPlane, o.normalPowerLog2, o.flags, o.staging};
+    check(pt_denoise_adaptive(m_ctx, &v, &p), "pt_denoise_adaptive");
+    m_denoised = true;
+}
+
+const float* Pathtracer::adaptiveVariance()
+{
+    if (m_group) check(PT_ERR_STATE, "adaptiveVariance: not available on a device group");
+    m_varianceBuffer.resize((size_t)localRows() * m_width);
+    check(pt_read_adaptive_variance(m_ctx, m_varianceBuffer.data()), "pt_read_adaptive_variance");
+    return m_varianceBuffer.data();
+}
+
 const float* Pathtracer::temporalHistory(uint32_t plane)
 {
     if (m_group) check(PT_ERR_STATE, "temporalHistory: not available on a device group");

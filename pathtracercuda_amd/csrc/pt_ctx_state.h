@@ -1,5 +1,6 @@
 // pt_ctx_state.h -- what a context carries from one call to the next, and every rule that moves it:
-// no HIP call, no context, plain values.  The C ABI functions (pt_kernels.hip, pt_denoise.h, pt_temporal.h, pt_svgf.h)
+// no HIP call, no context, plain values.  The C ABI functions (pt_kernels.hip, pt_denoise.h, pt_temporal.h, pt_svgf.h,
+// pt_adaptive_variance.h)
 // raise the events below and ask the predicates; they assign none of these fields themselves.
 // tools/ctx_state_check.cpp and tests/test_ctx_state.py run the same functions on the CPU.
 //
@@ -38,6 +39,10 @@
 //                   pt_temporal_moments, pt_read_temporal_variance, pt_denoise_variance): set when a moments
 //                   step is done, ended by whatever ends the history -- a pt_temporal step included, which
 //                   begins as every temporal pass and sets it no more.  Implies histValid.
+//   avValid         "the held variance is of the counts" (pt_read_adaptive_variance and its timing): set when a
+//                   pt_denoise_adaptive is done, ended by its beginning, by whatever ends adCountsValid (a launch
+//                   that writes the accumulation) and by the beginning of a features call (it was made with the
+//                   planes held then).  Implies adCountsValid.
 //   epoch           counts the launches that wrote the accumulation (a device group's gather cache
 //                   key, pt_group.h).  Never decreases.
 // A call refused for its arguments or for the state raises no event (but for a render whose plan is a
@@ -61,6 +66,7 @@ struct CtxState {
     bool featValid = false, dnValid = false;
     bool tpValid = false, histValid = false, tpOfPlanes = false;
     bool momValid = false;
+    bool avValid = false;
     uint64_t epoch = 0;
 };
 
@@ -128,6 +134,7 @@ inline RenderStart render_begins(CtxState& s, const pt_camera& cam)
 {
     s.adMomValid = false;                 // the moments and counts of an adaptive render no longer describe the buffer
     s.adCountsValid = false;
+    s.avValid = false;
     const bool sameCam = memcmp(&s.lastCam, &cam, sizeof(pt_camera)) == 0;
     const bool sameKey = s.launched && sameCam && s.lastState == s.stateEpoch;
     s.aheadMisses = sameKey ? 0u : std::min(s.aheadMisses + 1u, 1000u);
@@ -155,6 +162,7 @@ inline void adaptive_begins(CtxState& s)
     accum_written(s);
     s.adMomValid = false;                 // until the render is complete
     s.adCountsValid = false;
+    s.avValid = false;
 }
 
 inline void adaptive_done(CtxState& s)
@@ -167,6 +175,7 @@ inline void features_begin(CtxState& s)
 {
     s.featValid = false;
     s.tpOfPlanes = false;
+    s.avValid = false;
 }
 inline void features_done(CtxState& s) { s.featValid = true; }
 inline void denoise_begins(CtxState& s) { s.dnValid = false; }
@@ -186,6 +195,9 @@ inline void temporal_done(CtxState& s)
 }
 // a moments step raises temporal_begins, temporal_done and then this
 inline void moments_done(CtxState& s) { s.momValid = s.histValid; }
+// pt_denoise_adaptive raises denoise_begins, this, denoise_done and then adaptive_variance_done
+inline void adaptive_variance_begins(CtxState& s) { s.avValid = false; }
+inline void adaptive_variance_done(CtxState& s) { s.avValid = s.adCountsValid; }
 
 // ---- predicates -----------------------------------------------------------------------------------
 inline bool counts_describe_buffer(const CtxState& s) { return s.adCountsValid; }
@@ -196,5 +208,6 @@ inline bool holds_temporal(const CtxState& s) { return s.tpValid; }
 inline bool history_held(const CtxState& s) { return s.histValid; }
 inline bool temporal_of_planes(const CtxState& s) { return s.tpOfPlanes; }
 inline bool history_has_moments(const CtxState& s) { return s.momValid; }
+inline bool variance_of_counts(const CtxState& s) { return s.avValid; }
 
 } // namespace pt

@@ -449,6 +449,8 @@ __global__ void __launch_bounds__(256) adapt_scatter_kernel(const unsigned long 
 
 #include "pt_dev_svgf.h"
 
+#include "pt_dev_adaptive_variance.h"
+
 // Multi-device gather, second half: scatter one device's received rows (its bands, in local row
 // order) into the full image.  A band is band-rows consecutive image rows in both buffers, so every
 // lane copies one float4 of a coalesced row.
@@ -561,6 +563,10 @@ struct pt_context {
     hipEvent_t fbEv[2] = {};          // around the feedback kernel (pt_denoise_variance_feedback)
     float fbMs = 0.0f;
     bool fbRan = false;               // a feedback call has run since the last moments step
+    // the variance of an adaptive render's image (pt_adaptive_variance.h); no render state
+    float4* avBuf = nullptr;          // [2][pixels] the tap planes (N, l), (P, id), then [pixels] float: the variance
+    hipEvent_t avEv[2] = {};          // around adaptive_variance_kernel
+    float avMs = 0.0f;
     std::string err;
 };
 
@@ -867,11 +873,14 @@ PT_API void pt_destroy(pt_context* ctx)
     (void)hipFree(ctx->dnBuf);
     (void)hipFree(ctx->tpBuf);
     (void)hipFree(ctx->tmBuf);
+    (void)hipFree(ctx->avBuf);
     for (auto& e : ctx->dnEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->tmEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->fbEv)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : ctx->avEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& t : ctx->hostTex) (void)hipFree((void*)t.texels);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -1982,6 +1991,8 @@ PT_API int pt_set_kernel_variant(pt_context* ctx, int variant)
 #include "pt_temporal.h"
 
 #include "pt_svgf.h"
+
+#include "pt_adaptive_variance.h"
 
 extern "C" PT_API const char* pt_last_error(const pt_context* ctx)
 {

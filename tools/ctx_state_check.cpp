@@ -43,11 +43,12 @@ static pt_camera camera_of(unsigned long long id)
 static void (*const kEventFns[])(CtxState&) = {
     scene_or_texture_changed, rng_written, schedule_changed, order_dropped, order_replaced, order_biased,
     accum_written, stash_made, adaptive_begins, adaptive_done, features_begin, features_done, denoise_begins, denoise_done,
-    temporal_begins, temporal_done, moments_done};
+    temporal_begins, temporal_done, moments_done, adaptive_variance_begins, adaptive_variance_done};
 static const char* const kEventNames[] = {
     "scene_or_texture_changed", "rng_written", "schedule_changed", "order_dropped", "order_replaced",
     "order_biased", "accum_written", "stash_made", "adaptive_begins", "adaptive_done", "features_begin", "features_done",
-    "denoise_begins", "denoise_done", "temporal_begins", "temporal_done", "moments_done"};
+    "denoise_begins", "denoise_done", "temporal_begins", "temporal_done", "moments_done", "adaptive_variance_begins",
+    "adaptive_variance_done"};
 constexpr int kEvents = sizeof(kEventFns) / sizeof(kEventFns[0]);
 // the tool's own list of the events after which a sample is no longer what the last render's was
 static bool moves_epoch(void (*event)(CtxState&))
@@ -57,9 +58,11 @@ static bool moves_epoch(void (*event)(CtxState&))
 static_assert(kEvents == sizeof(kEventNames) / sizeof(kEventNames[0]), "one name per event");
 
 static bool (*const kPredicates[])(const CtxState&) = {counts_describe_buffer, moments_continue, planes_current, holds_denoised,
-                                                       holds_temporal, history_held, temporal_of_planes, history_has_moments};
+                                                       holds_temporal, history_held, temporal_of_planes, history_has_moments,
+                                                       variance_of_counts};
 static const char* const kPredicateNames[] = {"counts_describe_buffer", "moments_continue", "planes_current", "holds_denoised",
-                                              "holds_temporal", "history_held", "temporal_of_planes", "history_has_moments"};
+                                              "holds_temporal", "history_held", "temporal_of_planes", "history_has_moments",
+                                              "variance_of_counts"};
 constexpr int kPredicateCount = sizeof(kPredicates) / sizeof(kPredicates[0]);
 static_assert(kPredicateCount == sizeof(kPredicateNames) / sizeof(kPredicateNames[0]), "one name per predicate");
 
@@ -88,6 +91,7 @@ struct Fuzz {
     {
         const uint64_t stateEpoch = s.stateEpoch, epoch = s.epoch;
         const bool hist = s.histValid, mom = s.momValid;
+        const bool av = s.avValid, counts = s.adCountsValid;
         const uint32_t e = next() % (kEvents + 6);       // (a render as likely as four other events)
         if (e < (uint32_t)kEvents) {
             kEventFns[e](s);
@@ -107,11 +111,13 @@ struct Fuzz {
             check(r.stashMatches == (sh.stash && !sh.moved && sh.cam == cam));
             check(!s.aheadValid && s.launched && s.lastState == s.stateEpoch);
             check(r.aheadMisses == s.aheadMisses);
+            check(!s.avValid);                           // a render writes the accumulation
             sh = {true, false, false, cam};
         }
         check(!s.adMomValid || s.adCountsValid);
         check((!s.histValid || s.tpValid) && (!s.tpOfPlanes || s.tpValid));
         check(!s.momValid || s.histValid);
+        check(!s.avValid || s.adCountsValid);
         // the tool's own list of what ends a history and what does not
         if (e < (uint32_t)kEvents) {
             void (*const f)(CtxState&) = kEventFns[e];
@@ -121,8 +127,16 @@ struct Fuzz {
             // the moments end with the history (a plain temporal step begins as every step and sets them no more);
             // only a finished moments step over a held history sets them
             check(s.momValid == (f == moments_done ? hist : (mom && !ends)));
+            // the tool's own list of what ends the variance of the counts: what writes the accumulation (a render is
+            // checked above), a features call that begins, and the call that makes the next one; only a finished
+            // pt_denoise_adaptive over counts that describe the buffer sets it
+            const bool endsAv = f == adaptive_begins || f == features_begin || f == adaptive_variance_begins;
+            check(s.avValid == (f == adaptive_variance_done ? counts : (av && !endsAv)));
         } else if (e != (uint32_t)kEvents + 1) {
             check(s.histValid == hist && s.momValid == mom);     // a sort of the order, a render
+            if (e == (uint32_t)kEvents) check(s.avValid == av);
+        } else {
+            check(s.avValid == av);                              // a sky ends no variance of the counts
         }
         check(s.stateEpoch >= stateEpoch && s.epoch >= epoch);
         check(s.aheadMisses <= 1000u);
@@ -134,11 +148,11 @@ static void print_state(const CtxState& s, const std::string& extra)
     printf("{\"order\": {\"valid\": %d, \"stale\": %d, \"samples\": %llu, \"strip\": %u}, \"stateEpoch\": %llu, "
            "\"lastState\": %llu, \"launched\": %d, \"lastCam\": %d, \"aheadValid\": %d, \"aheadMisses\": %u, \"adMomValid\": %d, "
            "\"adCountsValid\": %d, \"featValid\": %d, \"dnValid\": %d, \"tpValid\": %d, \"histValid\": %d, "
-           "\"tpOfPlanes\": %d, \"momValid\": %d, \"epoch\": %llu%s}\n",
+           "\"tpOfPlanes\": %d, \"momValid\": %d, \"avValid\": %d, \"epoch\": %llu%s}\n",
            (int)s.order.valid, (int)s.order.stale, (unsigned long long)s.order.samples, s.order.strip,
            (unsigned long long)s.stateEpoch, (unsigned long long)s.lastState, (int)s.launched, (int)s.lastCam.origin[0],
            (int)s.aheadValid, s.aheadMisses, (int)s.adMomValid, (int)s.adCountsValid, (int)s.featValid, (int)s.dnValid,
-           (int)s.tpValid, (int)s.histValid, (int)s.tpOfPlanes, (int)s.momValid,
+           (int)s.tpValid, (int)s.histValid, (int)s.tpOfPlanes, (int)s.momValid, (int)s.avValid,
            (unsigned long long)s.epoch, extra.c_str());
     fflush(stdout);
 }
