@@ -235,6 +235,27 @@ public:
     float denoise(const DenoiseOptions& options);    // returns the sigma_color used
     float denoise() { return denoise(DenoiseOptions()); }
     bool denoised() const { return m_denoised; }     // the image calls return the denoised image
+    // Despike, the same-surface firefly clamp (pt_despike, rule 6 of pt_hip.h), after render and renderFeatures: a
+    // pixel whose luminance stands above `factor` times the `rank`-th largest of its same-surface neighbours within
+    // `radius`, plus `floor`, is scaled down to that limit; every other pixel keeps its words.  While the despiked
+    // image is held (until the next render, renderFeatures, scene, texture or sky change) getHDRImageData /
+    // getImageData return it and denoise() filters it (pt_denoise_despiked); the accumulation is not touched.
+    // despikeCount: the pixels the last despike clamped.  Single device only.
+    struct DespikeOptions {
+        uint32_t radius = PT_DESPIKE_DEFAULT_RADIUS;
+        uint32_t rank = PT_DESPIKE_DEFAULT_RANK;
+        float factor = PT_DESPIKE_DEFAULT_FACTOR;
+        float floor = PT_DESPIKE_DEFAULT_FLOOR;
+        uint32_t minNeighbors = 0;   // 0: PT_DESPIKE_DEFAULT_MIN_NEIGHBORS, raised to rank and lowered to the window's taps
+        float sigmaPlane = PT_DESPIKE_DEFAULT_SIGMA_PLANE;
+        float normalCosMin = PT_DESPIKE_DEFAULT_NORMAL_COS_MIN;
+        uint32_t flags = PT_DESPIKE_DEFAULT_FLAGS;
+        uint32_t staging = 0;
+    };
+    void despike(const DespikeOptions& options);
+    void despike() { despike(DespikeOptions()); }
+    uint32_t despikeCount();
+    bool despiked() const;                           // a despiked image made through this class is still held
     // Temporal reprojection (pt_temporal, pt_hip.h): per frame render(camera, spp, true), renderFeatures(camera),
     // temporal().  The result of the previous temporal() is reprojected into this frame's camera, rejected
     // where it is no longer the same surface, and this frame blended in.  Returns whether a previous history
@@ -331,6 +352,7 @@ private:
     float m_gatherMs = 0.0f;
     bool m_adaptive = false;
     bool m_denoised = false;
+    bool m_despiked = false;           // this class made a despiked image and nothing through it has ended it
     std::vector<float> m_featureBuffer;
     std::vector<float> m_temporalBuffer;
     std::vector<float> m_varianceBuffer;
@@ -357,6 +379,7 @@ struct Params {
     bool m_singleLaunch = true;      // run all chunks in one launch (bit-identical; CLI -call_loop: false)
     float m_adaptive = -1.0f;        // CLI -adaptive <tolerance>: >= 0 renders adaptively, m_spp is the budget
     unsigned int m_minSpp = 0;       // CLI -minspp: samples every pixel gets (0 = two calls)
+    bool m_despike = false;          // CLI -despike: the firefly clamp at its defaults before the image is written
     unsigned int m_denoise = 0;      // CLI -denoise [N]: a-trous iterations applied before the image is written (0 = off)
     bool m_denoiseAdaptive = false;  // CLI -denoise_guide adaptive: the filter follows the adaptive render's own variance
 };

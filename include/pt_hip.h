@@ -805,6 +805,90 @@ PT_API int pt_adaptive_variance_image(int device, uint32_t width, uint32_t heigh
                                       const float *moments, const pt_adaptive_variance_params *params,
                                       uint32_t staging, float *out_variance);
 
+/* ---- Despike: a same-surface firefly clamp ahead of the filters ------------------------------------
+ * An edge-stopping colour weight leaves a firefly where it is, and only the variance-guided filters pull an
+ * outlier in.  Rule 6 clamps a pixel whose luminance stands far above its same-surface neighbourhood's, before any
+ * filter sees it: one Jacobi pass (every neighbour is read unclamped, so no order of pixels matters).  All float32,
+ * no contraction, + - x /, compares and selects only; lum, "finite" and every dot product as above.
+ * tests/despike_model.py restates the rule.
+ *
+ * 6. Per pixel p: the colour C_p and the feature planes (A, id; N, t; P, flags).  Parameters: pt_despike_params.
+ *     D_p = pt_denoise's: per channel  A > 1/64 ? A : 1/64  when DEMODULATE, else 1;   I_p = C_p / D_p
+ *     l_p = lum(I_p)
+ *     ok_p = HIT && !EMISSIVE && l_p finite && every component of N_p, P_p finite        (rule 5's ok)
+ *     !ok_p:  out_p.xyz = C_p.xyz, and p is never anyone's neighbour
+ *     otherwise  top[0..3] = -inf, k = 0;  m = sigma_plane * t_p;  mm = m * m
+ *       for dy = -radius .. radius (outer), dx = -radius .. radius (inner), q = p + (dx, dy), the centre left out:
+ *       a tap is skipped (by a select; its index is clamped into the image before the load) when q is outside
+ *       the image, or !ok_q, or N_p . N_q < normal_cos_min, or with g = N_p . (P_q - P_p)  !(g*g <= mm), or
+ *       SAME_PRIMITIVE is set and id_q != id_p;  otherwise
+ *         k = k + 1;  v = l_q;  for j = 0 .. 3 in order:  if (v > top[j]) swap(v, top[j])
+ *       (top holds the four largest accepted luminances, largest first; the compare is strict and the taps come
+ *       in this order, which fixes which of +0 and -0 is kept)
+ *     k < min_neighbors:  out_p.xyz = C_p.xyz
+ *     otherwise  M = top[rank - 1];  limit = factor * M + floor;  spike = (limit >= 0) && (l_p > limit)
+ *       spike:   s = limit / l_p;  out_p.xyz = (I_p * s) * D_p          (per channel; s lies in [0, 1))
+ *       else:    out_p.xyz = C_p.xyz                                    (the input words, not I_p * D_p)
+ *     out_p.w = 1.   count = the number of spikes.
+ *    `rank` is how many equally bright neighbours a pixel may have and still be a spike: 1 catches single pixels,
+ *    2..4 catch clusters.  `floor` keeps a lone lit pixel among black neighbours from being scaled to zero.
+ *    Accepted: radius 1..3, rank 1..4, factor >= 1 and finite, floor >= 0 and finite, min_neighbors from rank to
+ *    (2 radius + 1)^2 - 1, sigma_plane >= 1e-6 and finite, normal_cos_min -1..1, flags within PT_DENOISE_DEMODULATE |
+ *    PT_DENOISE_SAME_PRIMITIVE, staging 0..2; anything else (a NaN included) is PT_ERR_ARG and the message names
+ *    the field.
+ *    Two kernels: a flat pass packs what a tap needs, (N, l) and (P, id), l not finite where the pixel is not ok
+ *    (rule 5's layout); despike_kernel runs on the filter's 32 x 8 tile, its taps either staged in LDS with a halo
+ *    of `radius` (staging 1) or read through the caches (2); 0 = automatic.  The words are the same. */
+/* Defaults of the layers above (C++ Pathtracer::despike, Python, the CLI's -despike), chosen by the sweep of
+ * tools/despike_probe.py (profiles/despike_probe.json, DESIGN.md 5.13, which also says what they cost in energy);
+ * sigma_plane and normal_cos_min are the shipped values of rule 2 (PT_TEMPORAL_DEFAULT_*). */
+#define PT_DESPIKE_DEFAULT_RADIUS 1
+#define PT_DESPIKE_DEFAULT_RANK 2
+#define PT_DESPIKE_DEFAULT_FACTOR 4.0f
+#define PT_DESPIKE_DEFAULT_FLOOR 0.2f
+#define PT_DESPIKE_DEFAULT_MIN_NEIGHBORS 3
+#define PT_DESPIKE_DEFAULT_SIGMA_PLANE 0.3f
+#define PT_DESPIKE_DEFAULT_NORMAL_COS_MIN 0.0f
+#define PT_DESPIKE_DEFAULT_FLAGS 2u
+typedef struct pt_despike_params {
+    uint32_t radius;         /* the window is (2 radius + 1)^2 - 1 taps */
+    uint32_t rank;           /* the limit follows the rank-th largest accepted neighbour */
+    float factor;
+    float floor;             /* in units of the (demodulated) luminance */
+    uint32_t min_neighbors;  /* accepted taps below which the pixel is left alone */
+    float sigma_plane;       /* relative to the hit distance */
+    float normal_cos_min;
+    uint32_t flags;          /* PT_DENOISE_DEMODULATE, PT_DENOISE_SAME_PRIMITIVE */
+    uint32_t staging;
+} pt_despike_params;
+
+/* Rule 6 on the context's image -- pt_denoise's: accumulation * (1 / max(frames, 1)), or accumulation / n per pixel
+ * while pt_holds_adaptive -- with the planes of the last pt_render_features; the result is the context's despiked
+ * image.  It refuses exactly what pt_denoise refuses, with the same codes (PT_ERR_ARG for the parameters and on a
+ * band partition, PT_ERR_STATE without current planes).  The accumulation, RNG, moments, counts, tile costs and
+ * run-ahead stash are not written, and a refused call changes nothing.
+ * "A despiked image is held, of the accumulation and the planes the context holds" from the end of this call until
+ * the next one begins, a launch writes the accumulation (a render, an adaptive render), pt_render_features begins,
+ * a scene or texture change, or a sky change to another handle. */
+PT_API int pt_despike(pt_context *ctx, uint32_t frames, const pt_despike_params *params);
+/* 1 while a despiked image is held, else 0 (as pt_holds_adaptive: a question, never an error). */
+PT_API int pt_holds_despiked(const pt_context *ctx);
+/* The held despiked image (rows x width float4, w = 1), its tonemap (pt_tonemap_denoised's arithmetic; RGBA8),
+ * the number of spikes (one uint32) and the hipEvent times in ms of the two kernels (2 floats: the flat pass,
+ * despike_kernel).  PT_ERR_STATE unless a despiked image is held. */
+PT_API int pt_read_despiked(pt_context *ctx, float *dst);
+PT_API int pt_tonemap_despiked(pt_context *ctx, uint8_t *dst);
+PT_API int pt_read_despike_count(pt_context *ctx, uint32_t *dst);
+PT_API int pt_read_despike_timing(pt_context *ctx, float *dst);
+/* pt_denoise's filter with the held despiked image as its colour (as pt_denoise_temporal takes the temporal
+ * image); the result goes where pt_denoise's goes.  PT_ERR_STATE unless a despiked image is held. */
+PT_API int pt_denoise_despiked(pt_context *ctx, const pt_denoise_params *params);
+/* Rule 6 on host arrays, without a context (as pt_denoise_image): color, plane0..2 and out are height x width
+ * float4 (color's w is ignored), out_count (optional) one uint32.  Errors: pt_last_error(NULL). */
+PT_API int pt_despike_image(int device, uint32_t width, uint32_t height, const float *color, const float *plane0,
+                            const float *plane1, const float *plane2, const pt_despike_params *params, float *out,
+                            uint32_t *out_count);
+
 /* ---- Multi-device group (one process, one context per GPU, RCCL over xGMI) -------------------
  * Replaces the reference's hard-coded single device (Pathtracer.cpp:40: cudaSetDevice(0)) behind
  * the same Pathtracer interface: device i renders the row bands b = i, i + N, ... of the image

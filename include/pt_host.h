@@ -118,6 +118,12 @@ PT_API const float *pth_renderer_temporal_history(pth_renderer *r, uint32_t plan
 PT_API int pth_renderer_denoise_adaptive(pth_renderer *r, const pt_adaptive_variance_params *variance,
                                          const pt_vdenoise_params *params);
 PT_API const float *pth_renderer_adaptive_variance(pth_renderer *r);
+/* Pathtracer::despike / despikeCount (pt_despike, pt_read_despike_count, pt_hip.h; single device).  After
+ * pth_renderer_despike the image calls return the despiked image and pth_renderer_denoise filters it, until the next
+ * render, features call or scene change.  params->min_neighbors 0 = the default (3, raised to rank and lowered to the
+ * window's taps).  pth_renderer_despike_count: the pixels clamped, into *count. */
+PT_API int pth_renderer_despike(pth_renderer *r, const pt_despike_params *params);
+PT_API int pth_renderer_despike_count(pth_renderer *r, uint32_t *count);
 PT_API float pth_renderer_timing(const pth_renderer *r);
 PT_API uint32_t pth_renderer_frames(const pth_renderer *r);
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer *r);

@@ -30,7 +30,8 @@ __all__ = ["Pathtracer", "Scene", "make_camera", "camera_rotate", "camera_transl
            "temporal_params", "temporal_image", "TEMPORAL_DEFAULTS", "variance_params", "vdenoise_params",
            "temporal_moments_image", "denoise_variance_image", "VARIANCE_DEFAULTS", "VDENOISE_DEFAULTS",
            "vfeedback_params", "denoise_variance_feedback_image", "VFEEDBACK_DEFAULTS", "adaptive_variance_params",
-           "adaptive_variance_image", "AVARIANCE_DEFAULTS", "ADENOISE_SIGMA_L"]
+           "adaptive_variance_image", "AVARIANCE_DEFAULTS", "ADENOISE_SIGMA_L", "despike_params", "despike_image",
+           "DESPIKE_DEFAULTS"]
 
 HITTABLE_TYPES = ["SPHERE", "CYLINDER", "DISK", "CONE", "PARABOLOID", "QUAD", "CUBE"]   # Hittable.h:9-12
 MATERIAL_TYPES = ["LAMBERT", "GGX", "LAMBERT_GGX"]                                     # Material.h:9-12
@@ -443,6 +444,78 @@ def adaptive_variance_image(color, plane0, plane1, plane2, moments, min_batches:
     return out
 
 
+# Defaults of despike, the same-surface firefly clamp (PT_DESPIKE_DEFAULT_* of include/pt_hip.h): radius, rank, factor,
+# floor and the flags are the choice of the sweep of tools/despike_probe.py (profiles/despike_probe.json; DESIGN.md
+# §5.13 says what they cost in energy); sigma_plane and normal_cos_min are the temporal pass's.
+DESPIKE_DEFAULTS = {"radius": 1, "rank": 2, "factor": 4.0, "floor": 0.2, "min_neighbors": 3, "sigma_plane": 0.3,
+                    "normal_cos_min": 0.0, "demodulate": False, "same_primitive": True}
+
+
+def despike_params(radius: Optional[int] = None, rank: Optional[int] = None, factor: Optional[float] = None,
+                   floor: Optional[float] = None, min_neighbors: Optional[int] = None, sigma_plane: Optional[float] = None,
+                   normal_cos_min: Optional[float] = None, demodulate: Optional[bool] = None,
+                   same_primitive: Optional[bool] = None, staging: int = 0) -> "N.PtDespikeParams":
+    """pt_despike_params from keyword arguments, refused here (PT_ERR_ARG naming the field) before any device call
+    when a value is outside the accepted range of include/pt_hip.h.  min_neighbors=None: the default, raised to
+    `rank` and lowered to the window's size where the default lies outside them."""
+    d = DESPIKE_DEFAULTS
+    radius = d["radius"] if radius is None else radius
+    rank = d["rank"] if rank is None else rank
+    factor = d["factor"] if factor is None else factor
+    floor = d["floor"] if floor is None else floor
+    sigma_plane = d["sigma_plane"] if sigma_plane is None else sigma_plane
+    normal_cos_min = d["normal_cos_min"] if normal_cos_min is None else normal_cos_min
+    demodulate = d["demodulate"] if demodulate is None else demodulate
+    same_primitive = d["same_primitive"] if same_primitive is None else same_primitive
+
+    def integer(name, v, lo, hi, what):
+        if isinstance(v, float) and not np.isfinite(v) or int(v) != v or not lo <= int(v) <= hi:
+            raise _refuse(f"despike: {name} must be {what}, not {v!r}")
+        return int(v)
+
+    radius = integer("radius", radius, 1, 3, "1..3")
+    rank = integer("rank", rank, 1, 4, "1..4")
+    taps = (2 * radius + 1) ** 2 - 1
+    if min_neighbors is None:
+        min_neighbors = min(max(d["min_neighbors"], rank), taps)
+    min_neighbors = integer("min_neighbors", min_neighbors, rank, taps, f"rank..(2 radius + 1)^2 - 1 = {rank}..{taps}")
+    fa, fo, sp, nc = (np.float32(v) for v in (factor, floor, sigma_plane, normal_cos_min))
+    if not (fa >= 1 and np.isfinite(fa)):
+        raise _refuse(f"despike: factor must be >= 1 and finite, not {factor!r}")
+    if not (fo >= 0 and np.isfinite(fo)):
+        raise _refuse(f"despike: floor must be >= 0 and finite, not {floor!r}")
+    if not (sp >= np.float32(1e-6) and np.isfinite(sp)):
+        raise _refuse(f"despike: sigma_plane must be >= 1e-6 and finite, not {sigma_plane!r}")
+    if not -1 <= nc <= 1:
+        raise _refuse(f"despike: normal_cos_min must be -1..1, not {normal_cos_min!r}")
+    if staging not in (0, 1, 2):
+        raise _refuse(f"despike: staging must be 0, 1 or 2, not {staging!r}")
+    flags = (N.PT_DENOISE_DEMODULATE if demodulate else 0) | (N.PT_DENOISE_SAME_PRIMITIVE if same_primitive else 0)
+    return N.PtDespikeParams(radius, rank, float(fa), float(fo), min_neighbors, float(sp), float(nc), flags, int(staging))
+
+
+def despike_image(color, plane0, plane1, plane2, radius: Optional[int] = None, rank: Optional[int] = None,
+                  factor: Optional[float] = None, floor: Optional[float] = None, min_neighbors: Optional[int] = None,
+                  sigma_plane: Optional[float] = None, normal_cos_min: Optional[float] = None,
+                  demodulate: Optional[bool] = None, same_primitive: Optional[bool] = None, staging: int = 0,
+                  device: int = 0, return_count: bool = False):
+    """pt_despike_image: despike (rule 6 of include/pt_hip.h) on host arrays (height x width x 4 float32: the colour
+    and the three feature planes), without a Pathtracer -- for a frame gathered from several GPUs, and ahead of the
+    other *_image forms.  Returns height x width x 4, or (image, number of spikes) with return_count."""
+    params = despike_params(radius, rank, factor, floor, min_neighbors, sigma_plane, normal_cos_min, demodulate,
+                            same_primitive, staging)
+    c = _image4("color", color)
+    planes = [_image4(f"plane{k}", p, c.shape) for k, p in enumerate((plane0, plane1, plane2))]
+    out = np.zeros_like(c)
+    count = C.c_uint32(0)
+    fp = C.POINTER(C.c_float)
+    rc = N.hip().pt_despike_image(int(device), c.shape[1], c.shape[0], c.ctypes.data_as(fp),
+                                  *[p.ctypes.data_as(fp) for p in planes], C.byref(params), out.ctypes.data_as(fp),
+                                  C.byref(count))
+    N.check_ctx(rc, None)
+    return (out, int(count.value)) if return_count else out
+
+
 class Scene:
     """A parsed scene file (no GPU): objects in file order, the SAH BVH, camera, textures."""
 
@@ -680,10 +753,20 @@ class Pathtracer:
         spread of its 7 x 7 same-surface window, whose plane and normal tests take `window_sigma_plane` and
         `normal_cos_min`; sigma_l (default ADENOISE_SIGMA_L), variance_floor and the rest are the filter's as with
         guide="variance".
+        source="despiked": the plain filter on the image the last despike() left (pt_denoise_despiked); only with
+        guide="color" and without feedback.
         Arguments out of range raise before any device call."""
         self._single("denoise")
-        if source not in ("accumulation", "temporal"):
-            raise _refuse(f"denoise: source must be 'accumulation' or 'temporal', not {source!r}")
+        if source not in ("accumulation", "temporal", "despiked"):
+            raise _refuse(f"denoise: source must be 'accumulation', 'temporal' or 'despiked', not {source!r}")
+        if source == "despiked":
+            if guide != "color":
+                raise _refuse("denoise: source='despiked' needs guide='color' (the moments of the variance-guided "
+                              "filters describe the unclamped colour)")
+            if feedback != 0:
+                raise _refuse("denoise: feedback is not used with source='despiked' (there is no temporal history to feed)")
+            if frames is not None:
+                raise _refuse("denoise: frames is not used with source='despiked' (despike() has divided already)")
         if guide not in ("color", "variance", "adaptive"):
             raise _refuse(f"denoise: guide must be 'color', 'variance' or 'adaptive', not {guide!r}")
         if guide == "adaptive":
@@ -732,6 +815,14 @@ class Pathtracer:
                 params.sigma_color = auto_sigma_color(self.temporal_image(), *planes, demodulate=demod)
             N.check_ctx(N.hip().pt_denoise_temporal(self._ctx, C.byref(params)), self._ctx)
             return self.denoised()
+        if source == "despiked":
+            if sigma_color is None:
+                planes = getattr(self, "_planes", None)
+                if planes is None:
+                    raise PathtracerError(N.PT_ERR_STATE, "denoise: no feature planes (call features(camera) first)")
+                params.sigma_color = auto_sigma_color(self.despiked(), *planes, demodulate=demod)
+            N.check_ctx(N.hip().pt_denoise_despiked(self._ctx, C.byref(params)), self._ctx)
+            return self.denoised()
         f = self.frames if frames is None else int(frames)
         if sigma_color is None:
             planes = getattr(self, "_planes", None)
@@ -745,6 +836,55 @@ class Pathtracer:
             params.sigma_color = auto_sigma_color(color, *planes, demodulate=demod)
         N.check_ctx(N.hip().pt_denoise(self._ctx, f, C.byref(params)), self._ctx)
         return self.denoised()
+
+    # --- despike, the same-surface firefly clamp (pt_despike; rule 6 of pt_hip.h) ---------------------
+    def despike(self, radius: Optional[int] = None, rank: Optional[int] = None, factor: Optional[float] = None,
+                floor: Optional[float] = None, min_neighbors: Optional[int] = None, sigma_plane: Optional[float] = None,
+                normal_cos_min: Optional[float] = None, demodulate: Optional[bool] = None,
+                same_primitive: Optional[bool] = None, staging: int = 0, frames: Optional[int] = None) -> np.ndarray:
+        """Clamp the fireflies of the image (include/pt_hip.h, rule 6): a pixel whose luminance is above `factor`
+        times the `rank`-th largest of its same-surface neighbours within `radius`, plus `floor`, is scaled down to
+        that limit; every other pixel keeps its words.  Guided by the planes of the last features(camera) call;
+        returns rows x width x 4 float32 in get_hdr_image_data()'s units and leaves the accumulation as it is.
+        denoise(source="despiked") filters the result; despike_count() tells how many pixels were clamped.
+        Arguments out of range raise before any device call."""
+        self._single("despike")
+        params = despike_params(radius, rank, factor, floor, min_neighbors, sigma_plane, normal_cos_min, demodulate,
+                                same_primitive, staging)
+        f = self.frames if frames is None else int(frames)
+        if not 0 <= f <= 0xffffffff:
+            raise _refuse(f"despike: frames must be 0..2^32 - 1, not {frames!r}")
+        N.check_ctx(N.hip().pt_despike(self._ctx, f, C.byref(params)), self._ctx)
+        return self.despiked()
+
+    def despiked(self) -> np.ndarray:
+        """The held despiked image again (pt_read_despiked): until a render, features(), or a scene, texture or sky
+        change."""
+        self._single("despiked")
+        out = np.zeros((self.rows, self.width, 4), dtype=np.float32)
+        N.check_ctx(N.hip().pt_read_despiked(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float))), self._ctx)
+        return out
+
+    def tonemap_despiked(self) -> np.ndarray:
+        """The held despiked image through the tonemap (RGBA8, rows x width)."""
+        self._single("tonemap_despiked")
+        out = np.zeros((self.rows, self.width, 4), dtype=np.uint8)
+        N.check_ctx(N.hip().pt_tonemap_despiked(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint8))), self._ctx)
+        return out
+
+    def despike_count(self) -> int:
+        """The number of pixels the last despike() clamped (pt_read_despike_count)."""
+        self._single("despike_count")
+        n = C.c_uint32(0)
+        N.check_ctx(N.hip().pt_read_despike_count(self._ctx, C.byref(n)), self._ctx)
+        return int(n.value)
+
+    def despike_timing(self) -> Dict[str, float]:
+        """Kernel times of the last despike() in ms (hipEvents): {"prepare", "despike"}."""
+        self._single("despike_timing")
+        ms = (C.c_float * 2)()
+        N.check_ctx(N.hip().pt_read_despike_timing(self._ctx, ms), self._ctx)
+        return {"prepare": float(ms[0]), "despike": float(ms[1])}
 
     def adaptive_variance(self) -> np.ndarray:
         """The per-pixel variance the last denoise(guide="adaptive") made (pt_read_adaptive_variance): rows x width

@@ -96,6 +96,13 @@ class PtAdaptiveVarianceParams(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class PtDespikeParams(C.Structure):
+    """pt_despike_params (pt_hip.h, the same-surface firefly clamp)."""
+    _fields_ = [("radius", C.c_uint32), ("rank", C.c_uint32), ("factor", C.c_float), ("floor", C.c_float),
+                ("min_neighbors", C.c_uint32), ("sigma_plane", C.c_float), ("normal_cos_min", C.c_float),
+                ("flags", C.c_uint32), ("staging", C.c_uint32)]
+
+
 PT_FEATURE_HIT, PT_FEATURE_EMISSIVE = 1, 2
 PT_TEMPORAL_DEMODULATE, PT_TEMPORAL_SAME_PRIMITIVE = 1, 2
 PT_DENOISE_DEMODULATE, PT_DENOISE_SAME_PRIMITIVE = 1, 2
@@ -190,6 +197,15 @@ _HIP_SYMBOLS = {
     "pt_read_adaptive_variance_timing": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "pt_adaptive_variance_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 5
                                    + [P(PtAdaptiveVarianceParams), C.c_uint32, P(C.c_float)]),
+    "pt_despike": (C.c_int, [C.c_void_p, C.c_uint32, P(PtDespikeParams)]),
+    "pt_holds_despiked": (C.c_int, [C.c_void_p]),
+    "pt_read_despiked": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_tonemap_despiked": (C.c_int, [C.c_void_p, P(C.c_uint8)]),
+    "pt_read_despike_count": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
+    "pt_read_despike_timing": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_denoise_despiked": (C.c_int, [C.c_void_p, P(PtDenoiseParams)]),
+    "pt_despike_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 4
+                         + [P(PtDespikeParams), P(C.c_float), P(C.c_uint32)]),
     "pt_group_create": (C.c_int, [C.c_int, P(C.c_int), C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_void_p)]),
     "pt_group_destroy": (None, [C.c_void_p]),
     "pt_group_size": (C.c_int, [C.c_void_p]),
@@ -246,6 +262,8 @@ _HOST_SYMBOLS = {
     "pth_renderer_temporal_history": (P(C.c_float), [C.c_void_p, C.c_uint32]),
     "pth_renderer_denoise_adaptive": (C.c_int, [C.c_void_p, P(PtAdaptiveVarianceParams), P(PtVDenoiseParams)]),
     "pth_renderer_adaptive_variance": (P(C.c_float), [C.c_void_p]),
+    "pth_renderer_despike": (C.c_int, [C.c_void_p, P(PtDespikeParams)]),
+    "pth_renderer_despike_count": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
     "pth_renderer_timing": (C.c_float, [C.c_void_p]),
     "pth_renderer_frames": (C.c_uint32, [C.c_void_p]),
     "pth_renderer_local_rows": (C.c_uint32, [C.c_void_p]),

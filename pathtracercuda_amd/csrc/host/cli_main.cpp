@@ -17,6 +17,10 @@
 //                  with -adaptive and -denoise: the filter's colour weight follows a per-pixel variance made from
 //                  the adaptive render's own moments (Pathtracer::denoiseAdaptive) instead of one colour sigma
 //                  for the image.  Without both of them the option is invalid.
+//   -despike       clamp fireflies before -o / -ohdr write the image: a pixel far brighter than its same-surface
+//                  neighbours is scaled down to their level (Pathtracer::renderFeatures + despike, the parameters
+//                  at their defaults).  With -denoise the filter runs on the despiked image.  One GPU; not with
+//                  -denoise_guide adaptive, whose variance describes the unclamped colour.
 // The windowed / interactive mode (-window, -enable_controls) is not supported.
 #include <algorithm>
 #include <cstdio>
@@ -103,6 +107,7 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
             i += 2;
             continue;
         }
+        if (strcmp(argv[i], "-despike") == 0) { params.m_despike = true; ++i; continue; }
         if (strcmp(argv[i], "-minspp") == 0) { uintArg(i, "-minspp", params.m_minSpp); i += 2; continue; }
         printf("Can't parse argument: %s\n", argv[i]);
         displayHelp = true;
@@ -110,6 +115,10 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
     }
     if (params.m_denoiseAdaptive && !(params.m_adaptive >= 0.0f && params.m_denoise)) {
         printf("Invalid input for -denoise_guide! (adaptive needs both -adaptive and -denoise)\n");
+        displayHelp = true;
+    }
+    if (params.m_despike && params.m_denoiseAdaptive) {
+        printf("Invalid input for -despike! (not with -denoise_guide adaptive)\n");
         displayHelp = true;
     }
     // (`pathtracer -help` alone lists the options: the lone argument is not an input file)
@@ -140,6 +149,7 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
                "-denoise [N]");
         printf("%-30s With -adaptive and -denoise: guide the filter by the adaptive render's own per-pixel variance\n",
                "-denoise_guide adaptive");
+        printf("%-30s Clamp fireflies before writing (and before -denoise): same-surface neighbourhood limit\n", "-despike");
         return false;
     }
     params.m_enableControls = params.m_enableControls && params.m_showWindow;
@@ -176,6 +186,10 @@ int main(int argc, char* argv[])
     const bool adaptive = params.m_adaptive >= 0.0f;
     if (params.m_denoise && gpus > 1) {
         printf("-denoise renders on one GPU; ignoring -gpus.\n");
+        gpus = 1;
+    }
+    if (params.m_despike && gpus > 1) {
+        printf("-despike renders on one GPU; ignoring -gpus.\n");
         gpus = 1;
     }
     if (adaptive && gpus > 1) {
@@ -223,6 +237,11 @@ int main(int argc, char* argv[])
     }
     if (!adaptive) printf("Finished accumulating %d samples in %f ms GPU time\n", (int)params.m_spp, totalGpuTime);
 
+    if (params.m_despike) {
+        pathtracer->renderFeatures(camera);
+        pathtracer->despike();
+        printf("Despiked: %u pixels clamped\n", pathtracer->despikeCount());
+    }
     if (params.m_denoise && params.m_denoiseAdaptive) {
         Pathtracer::VarianceDenoiseOptions options;
         options.iterations = params.m_denoise;
@@ -233,7 +252,7 @@ int main(int argc, char* argv[])
     } else if (params.m_denoise) {
         Pathtracer::DenoiseOptions options;
         options.iterations = params.m_denoise;
-        pathtracer->renderFeatures(camera);
+        if (!params.m_despike) pathtracer->renderFeatures(camera);     // (a features call would end the despiked image)
         const float sigma = pathtracer->denoise(options);
         printf("Denoised: %u a-trous iterations, colour sigma %g\n", options.iterations, sigma);
     }

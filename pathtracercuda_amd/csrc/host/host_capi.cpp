@@ -461,6 +461,34 @@ PT_API const float* pth_renderer_adaptive_variance(pth_renderer* r)
     return nullptr;
 }
 
+PT_API int pth_renderer_despike(pth_renderer* r, const pt_despike_params* params)
+{
+    if (!r || !params) return setError(PT_ERR_ARG, "invalid argument");
+    PTH_GUARD_BEGIN
+    Pathtracer::DespikeOptions o;
+    o.radius = params->radius;
+    o.rank = params->rank;
+    o.factor = params->factor;
+    o.floor = params->floor;
+    o.minNeighbors = params->min_neighbors;
+    o.sigmaPlane = params->sigma_plane;
+    o.normalCosMin = params->normal_cos_min;
+    o.flags = params->flags;
+    o.staging = params->staging;
+    r->pt->despike(o);
+    return PT_OK;
+    PTH_GUARD_END
+}
+
+PT_API int pth_renderer_despike_count(pth_renderer* r, uint32_t* count)
+{
+    if (!r || !count) return setError(PT_ERR_ARG, "invalid argument");
+    PTH_GUARD_BEGIN
+    *count = r->pt->despikeCount();
+    return PT_OK;
+    PTH_GUARD_END
+}
+
 PT_API float pth_renderer_timing(const pth_renderer* r) { return r ? r->pt->getTiming() : 0.0f; }
 PT_API uint32_t pth_renderer_frames(const pth_renderer* r) { return r ? r->pt->accumulatedFrames() : 0; }
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer* r) { return r ? r->pt->localRows() : 0; }

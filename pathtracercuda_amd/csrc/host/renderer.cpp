@@ -100,6 +100,7 @@ void Pathtracer::setScene(size_t count, const CpuHittable* hittables)
     m_nodeCount = (uint32_t)dn.size();
     m_hittableCount = (uint32_t)dp.size();
     m_denoised = false;
+    m_despiked = false;
 }
 
 void Pathtracer::render(const Camera& camera, uint32_t spp, bool ignoreHistory)
@@ -123,6 +124,7 @@ void Pathtracer::renderChunks(const Camera& camera, uint32_t spp, uint32_t chunk
     // nothing (spp or chunks 0) leaves an adaptive buffer adaptive
     m_adaptive = adaptive();
     m_denoised = false;
+    m_despiked = false;
     if (ignoreHistory) m_accumulatedFrames = 0;
     m_timing = ms;
     m_accumulatedFrames += chunks;
@@ -145,6 +147,7 @@ Pathtracer::AdaptiveResult Pathtracer::renderAdaptive(const Camera& camera, uint
     m_timing = res.gpu_ms;
     m_adaptive = true;
     m_denoised = false;
+    m_despiked = false;
     m_accumulatedFrames = 0;          // the per-pixel counts describe the buffer now
     return AdaptiveResult{res.rounds, res.samples, res.gpu_ms};
 }
@@ -154,6 +157,7 @@ void Pathtracer::renderFeatures(const Camera& camera)
     if (m_group) check(PT_ERR_STATE, "renderFeatures: not available on a device group");
     const pt_camera cam = camera.toDevice();
     check(pt_render_features(m_ctx, &cam), "pt_render_features");
+    m_despiked = false;               // a despiked image was of the planes held before
 }
 
 const float* Pathtracer::featurePlane(uint32_t plane)
@@ -206,9 +210,35 @@ float Pathtracer::denoise(const DenoiseOptions& o)
             if (med > 0.0f && std::isfinite(med)) p.sigma_color = PT_DENOISE_DEFAULT_SIGMA_FACTOR * med;
         }
     }
-    check(pt_denoise(m_ctx, m_accumulatedFrames, &p), "pt_denoise");
+    if (despiked()) check(pt_denoise_despiked(m_ctx, &p), "pt_denoise_despiked");
+    else check(pt_denoise(m_ctx, m_accumulatedFrames, &p), "pt_denoise");
     m_denoised = true;
     return p.sigma_color;
+}
+
+void Pathtracer::despike(const DespikeOptions& o)
+{
+    if (m_group) check(PT_ERR_STATE, "despike: not available on a device group");
+    // minNeighbors 0: the default, raised to rank and lowered to what the window has (Python's rule)
+    const uint32_t side = 2u * o.radius + 1u, taps = side * side - 1u;
+    const uint32_t minNeighbors = o.minNeighbors ? o.minNeighbors
+                                                 : std::min(std::max((uint32_t)PT_DESPIKE_DEFAULT_MIN_NEIGHBORS, o.rank), taps);
+    const pt_despike_params p = {o.radius, o.rank, o.factor, o.floor, minNeighbors, o.sigmaPlane, o.normalCosMin, o.flags, o.staging};
+    check(pt_despike(m_ctx, m_accumulatedFrames, &p), "pt_despike");
+    m_despiked = true;
+    m_denoised = false;               // a denoised image was of the image before the clamp
+}
+
+// m_despiked says that this class made a despiked image and has ended it nowhere; the device context says whether
+// it is still held (a call on the context, past this class, ends it too)
+bool Pathtracer::despiked() const { return m_despiked && !m_group && pt_holds_despiked(m_ctx) != 0; }
+
+uint32_t Pathtracer::despikeCount()
+{
+    if (m_group) check(PT_ERR_STATE, "despikeCount: not available on a device group");
+    uint32_t n = 0;
+    check(pt_read_despike_count(m_ctx, &n), "pt_read_despike_count");
+    return n;
 }
 
 bool Pathtracer::temporal(const TemporalOptions& o, bool reset)
@@ -300,11 +330,13 @@ uint32_t Pathtracer::loadTexture(const char* path)
     if (m_group) check(pt_group_set_texture(m_group, m_textureCount + 1, rgba.data(), w, h), "pt_group_set_texture");
     else check(pt_set_texture(m_ctx, m_textureCount + 1, rgba.data(), w, h), "pt_set_texture");
     ++m_textureCount;
+    m_despiked = false;
     return m_textureCount;
 }
 
 void Pathtracer::setSkyboxTextureHandle(uint32_t handle)
 {
+    if (handle != m_skyboxTextureHandle) m_despiked = false;     // the image's colours are of the old sky
     m_skyboxTextureHandle = handle;
     if (m_group) check(pt_group_set_skybox(m_group, handle), "pt_group_set_skybox");
     else check(pt_set_skybox(m_ctx, handle), "pt_set_skybox");
@@ -314,6 +346,10 @@ float* Pathtracer::getHDRImageData()
 {
     if (m_denoised) {
         check(pt_read_denoised(m_ctx, m_cpuAccumBuffer.data()), "pt_read_denoised");
+        return m_cpuAccumBuffer.data();
+    }
+    if (despiked()) {
+        check(pt_read_despiked(m_ctx, m_cpuAccumBuffer.data()), "pt_read_despiked");
         return m_cpuAccumBuffer.data();
     }
     if (adaptive()) {                 // every pixel over its own number of calls
@@ -335,6 +371,10 @@ char* Pathtracer::getImageData()
 {
     if (m_denoised) {
         check(pt_tonemap_denoised(m_ctx, (uint8_t*)m_cpuResultBuffer.data()), "pt_tonemap_denoised");
+        return m_cpuResultBuffer.data();
+    }
+    if (despiked()) {
+        check(pt_tonemap_despiked(m_ctx, (uint8_t*)m_cpuResultBuffer.data()), "pt_tonemap_despiked");
         return m_cpuResultBuffer.data();
     }
     if (adaptive()) {

@@ -1,6 +1,6 @@
 // pt_ctx_state.h -- what a context carries from one call to the next, and every rule that moves it:
 // no HIP call, no context, plain values.  The C ABI functions (pt_kernels.hip, pt_denoise.h, pt_temporal.h, pt_svgf.h,
-// pt_adaptive_variance.h)
+// pt_adaptive_variance.h, pt_despike.h)
 // raise the events below and ask the predicates; they assign none of these fields themselves.
 // tools/ctx_state_check.cpp and tests/test_ctx_state.py run the same functions on the CPU.
 //
@@ -43,6 +43,11 @@
 //                   pt_denoise_adaptive is done, ended by its beginning, by whatever ends adCountsValid (a launch
 //                   that writes the accumulation) and by the beginning of a features call (it was made with the
 //                   planes held then).  Implies adCountsValid.
+//   dsValid         "a despiked image is held, of the accumulation and the planes the context holds" (pt_read_despiked,
+//                   its tonemap, count and timing, pt_denoise_despiked): set when a pt_despike is done, ended by its
+//                   beginning, by a launch that writes the accumulation (a render, an adaptive render), by the
+//                   beginning of a features call, by a scene or texture change and by a sky change to another handle.
+//                   An RNG write and a camera change end nothing: neither touches the image or the planes.
 //   epoch           counts the launches that wrote the accumulation (a device group's gather cache
 //                   key, pt_group.h).  Never decreases.
 // A call refused for its arguments or for the state raises no event (but for a render whose plan is a
@@ -67,6 +72,7 @@ struct CtxState {
     bool tpValid = false, histValid = false, tpOfPlanes = false;
     bool momValid = false;
     bool avValid = false;
+    bool dsValid = false;
     uint64_t epoch = 0;
 };
 
@@ -79,6 +85,7 @@ inline void scene_or_texture_changed(CtxState& s)
     s.featValid = false;
     s.histValid = false;
     s.momValid = false;
+    s.dsValid = false;
     ++s.stateEpoch;
 }
 
@@ -91,6 +98,7 @@ inline void sky_set(CtxState& s, uint32_t held, uint32_t handle)
     s.adMomValid = false;
     s.histValid = false;
     s.momValid = false;
+    s.dsValid = false;
 }
 
 // pt_write_rng: a stash and the moments continue the old streams
@@ -135,6 +143,7 @@ inline RenderStart render_begins(CtxState& s, const pt_camera& cam)
     s.adMomValid = false;                 // the moments and counts of an adaptive render no longer describe the buffer
     s.adCountsValid = false;
     s.avValid = false;
+    s.dsValid = false;
     const bool sameCam = memcmp(&s.lastCam, &cam, sizeof(pt_camera)) == 0;
     const bool sameKey = s.launched && sameCam && s.lastState == s.stateEpoch;
     s.aheadMisses = sameKey ? 0u : std::min(s.aheadMisses + 1u, 1000u);
@@ -163,6 +172,7 @@ inline void adaptive_begins(CtxState& s)
     s.adMomValid = false;                 // until the render is complete
     s.adCountsValid = false;
     s.avValid = false;
+    s.dsValid = false;
 }
 
 inline void adaptive_done(CtxState& s)
@@ -176,6 +186,7 @@ inline void features_begin(CtxState& s)
     s.featValid = false;
     s.tpOfPlanes = false;
     s.avValid = false;
+    s.dsValid = false;
 }
 inline void features_done(CtxState& s) { s.featValid = true; }
 inline void denoise_begins(CtxState& s) { s.dnValid = false; }
@@ -198,6 +209,9 @@ inline void moments_done(CtxState& s) { s.momValid = s.histValid; }
 // pt_denoise_adaptive raises denoise_begins, this, denoise_done and then adaptive_variance_done
 inline void adaptive_variance_begins(CtxState& s) { s.avValid = false; }
 inline void adaptive_variance_done(CtxState& s) { s.avValid = s.adCountsValid; }
+inline void despike_begins(CtxState& s) { s.dsValid = false; }
+// (pt_despike has checked planes_current, and nothing between its two events can end the planes)
+inline void despike_done(CtxState& s) { s.dsValid = s.featValid; }
 
 // ---- predicates -----------------------------------------------------------------------------------
 inline bool counts_describe_buffer(const CtxState& s) { return s.adCountsValid; }
@@ -209,5 +223,6 @@ inline bool history_held(const CtxState& s) { return s.histValid; }
 inline bool temporal_of_planes(const CtxState& s) { return s.tpOfPlanes; }
 inline bool history_has_moments(const CtxState& s) { return s.momValid; }
 inline bool variance_of_counts(const CtxState& s) { return s.avValid; }
+inline bool holds_despiked(const CtxState& s) { return s.dsValid; }
 
 } // namespace pt

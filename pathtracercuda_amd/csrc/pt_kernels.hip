@@ -451,6 +451,8 @@ __global__ void __launch_bounds__(256) adapt_scatter_kernel(const unsigned long 
 
 #include "pt_dev_adaptive_variance.h"
 
+#include "pt_dev_despike.h"
+
 // Multi-device gather, second half: scatter one device's received rows (its bands, in local row
 // order) into the full image.  A band is band-rows consecutive image rows in both buffers, so every
 // lane copies one float4 of a coalesced row.
@@ -567,6 +569,11 @@ struct pt_context {
     float4* avBuf = nullptr;          // [2][pixels] the tap planes (N, l), (P, id), then [pixels] float: the variance
     hipEvent_t avEv[2] = {};          // around adaptive_variance_kernel
     float avMs = 0.0f;
+    // despike (pt_despike.h); no render state
+    float4* dsBuf = nullptr;          // [pixels] the colour, [2][pixels] the tap planes (N, l), (P, id), [pixels] the despiked image, the count
+    hipEvent_t dsEv[3] = {};          // before the flat pass, between the kernels, after despike_kernel
+    float dsMs[2] = {};
+    uint32_t dsCount = 0;
     std::string err;
 };
 
@@ -874,6 +881,7 @@ PT_API void pt_destroy(pt_context* ctx)
     (void)hipFree(ctx->tpBuf);
     (void)hipFree(ctx->tmBuf);
     (void)hipFree(ctx->avBuf);
+    (void)hipFree(ctx->dsBuf);
     for (auto& e : ctx->dnEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->tmEv)
@@ -881,6 +889,8 @@ PT_API void pt_destroy(pt_context* ctx)
     for (auto& e : ctx->fbEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->avEv)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : ctx->dsEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& t : ctx->hostTex) (void)hipFree((void*)t.texels);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -1993,6 +2003,8 @@ PT_API int pt_set_kernel_variant(pt_context* ctx, int variant)
 #include "pt_svgf.h"
 
 #include "pt_adaptive_variance.h"
+
+#include "pt_despike.h"
 
 extern "C" PT_API const char* pt_last_error(const pt_context* ctx)
 {

@@ -43,12 +43,13 @@ static pt_camera camera_of(unsigned long long id)
 static void (*const kEventFns[])(CtxState&) = {
     scene_or_texture_changed, rng_written, schedule_changed, order_dropped, order_replaced, order_biased,
     accum_written, stash_made, adaptive_begins, adaptive_done, features_begin, features_done, denoise_begins, denoise_done,
-    temporal_begins, temporal_done, moments_done, adaptive_variance_begins, adaptive_variance_done};
+    temporal_begins, temporal_done, moments_done, adaptive_variance_begins, adaptive_variance_done, despike_begins,
+    despike_done};
 static const char* const kEventNames[] = {
     "scene_or_texture_changed", "rng_written", "schedule_changed", "order_dropped", "order_replaced",
     "order_biased", "accum_written", "stash_made", "adaptive_begins", "adaptive_done", "features_begin", "features_done",
     "denoise_begins", "denoise_done", "temporal_begins", "temporal_done", "moments_done", "adaptive_variance_begins",
-    "adaptive_variance_done"};
+    "adaptive_variance_done", "despike_begins", "despike_done"};
 constexpr int kEvents = sizeof(kEventFns) / sizeof(kEventFns[0]);
 // the tool's own list of the events after which a sample is no longer what the last render's was
 static bool moves_epoch(void (*event)(CtxState&))
@@ -59,10 +60,10 @@ static_assert(kEvents == sizeof(kEventNames) / sizeof(kEventNames[0]), "one name
 
 static bool (*const kPredicates[])(const CtxState&) = {counts_describe_buffer, moments_continue, planes_current, holds_denoised,
                                                        holds_temporal, history_held, temporal_of_planes, history_has_moments,
-                                                       variance_of_counts};
+                                                       variance_of_counts, holds_despiked};
 static const char* const kPredicateNames[] = {"counts_describe_buffer", "moments_continue", "planes_current", "holds_denoised",
                                               "holds_temporal", "history_held", "temporal_of_planes", "history_has_moments",
-                                              "variance_of_counts"};
+                                              "variance_of_counts", "holds_despiked"};
 constexpr int kPredicateCount = sizeof(kPredicates) / sizeof(kPredicates[0]);
 static_assert(kPredicateCount == sizeof(kPredicateNames) / sizeof(kPredicateNames[0]), "one name per predicate");
 
@@ -92,6 +93,7 @@ struct Fuzz {
         const uint64_t stateEpoch = s.stateEpoch, epoch = s.epoch;
         const bool hist = s.histValid, mom = s.momValid;
         const bool av = s.avValid, counts = s.adCountsValid;
+        const bool ds = s.dsValid, feat = s.featValid;
         const uint32_t e = next() % (kEvents + 6);       // (a render as likely as four other events)
         if (e < (uint32_t)kEvents) {
             kEventFns[e](s);
@@ -105,6 +107,7 @@ struct Fuzz {
             if (held != handle) sh.moved = true;
             check(s.histValid == (hist && held == handle));
             check(s.momValid == (mom && held == handle));
+            check(s.dsValid == (ds && held == handle));          // another sky: the image's colours are of the old one
         } else {
             const unsigned long long cam = next() % 3;
             const RenderStart r = render_begins(s, camera_of(cam));
@@ -112,12 +115,14 @@ struct Fuzz {
             check(!s.aheadValid && s.launched && s.lastState == s.stateEpoch);
             check(r.aheadMisses == s.aheadMisses);
             check(!s.avValid);                           // a render writes the accumulation
+            check(!s.dsValid);
             sh = {true, false, false, cam};
         }
         check(!s.adMomValid || s.adCountsValid);
         check((!s.histValid || s.tpValid) && (!s.tpOfPlanes || s.tpValid));
         check(!s.momValid || s.histValid);
         check(!s.avValid || s.adCountsValid);
+        check(!s.dsValid || s.featValid);                // the despiked image is of the planes the context holds
         // the tool's own list of what ends a history and what does not
         if (e < (uint32_t)kEvents) {
             void (*const f)(CtxState&) = kEventFns[e];
@@ -132,9 +137,14 @@ struct Fuzz {
             // pt_denoise_adaptive over counts that describe the buffer sets it
             const bool endsAv = f == adaptive_begins || f == features_begin || f == adaptive_variance_begins;
             check(s.avValid == (f == adaptive_variance_done ? counts : (av && !endsAv)));
+            // the tool's own list of what ends the despiked image: its own beginning, what writes the accumulation (a
+            // render is checked above), a features call that begins, a scene or texture change (another sky is checked
+            // above); only a finished pt_despike over current planes sets it
+            const bool endsDs = f == despike_begins || f == adaptive_begins || f == features_begin || f == scene_or_texture_changed;
+            check(s.dsValid == (f == despike_done ? feat : (ds && !endsDs)));
         } else if (e != (uint32_t)kEvents + 1) {
             check(s.histValid == hist && s.momValid == mom);     // a sort of the order, a render
-            if (e == (uint32_t)kEvents) check(s.avValid == av);
+            if (e == (uint32_t)kEvents) check(s.avValid == av && s.dsValid == ds);
         } else {
             check(s.avValid == av);                              // a sky ends no variance of the counts
         }
@@ -148,11 +158,11 @@ static void print_state(const CtxState& s, const std::string& extra)
     printf("{\"order\": {\"valid\": %d, \"stale\": %d, \"samples\": %llu, \"strip\": %u}, \"stateEpoch\": %llu, "
            "\"lastState\": %llu, \"launched\": %d, \"lastCam\": %d, \"aheadValid\": %d, \"aheadMisses\": %u, \"adMomValid\": %d, "
            "\"adCountsValid\": %d, \"featValid\": %d, \"dnValid\": %d, \"tpValid\": %d, \"histValid\": %d, "
-           "\"tpOfPlanes\": %d, \"momValid\": %d, \"avValid\": %d, \"epoch\": %llu%s}\n",
+           "\"tpOfPlanes\": %d, \"momValid\": %d, \"avValid\": %d, \"dsValid\": %d, \"epoch\": %llu%s}\n",
            (int)s.order.valid, (int)s.order.stale, (unsigned long long)s.order.samples, s.order.strip,
            (unsigned long long)s.stateEpoch, (unsigned long long)s.lastState, (int)s.launched, (int)s.lastCam.origin[0],
            (int)s.aheadValid, s.aheadMisses, (int)s.adMomValid, (int)s.adCountsValid, (int)s.featValid, (int)s.dnValid,
-           (int)s.tpValid, (int)s.histValid, (int)s.tpOfPlanes, (int)s.momValid, (int)s.avValid,
+           (int)s.tpValid, (int)s.histValid, (int)s.tpOfPlanes, (int)s.momValid, (int)s.avValid, (int)s.dsValid,
            (unsigned long long)s.epoch, extra.c_str());
     fflush(stdout);
 }
