@@ -195,6 +195,18 @@ public:
     ~Pathtracer();
 
     void setScene(size_t count, const CpuHittable* hittables);
+    // setScene for a scene whose objects moved since the last setScene / setSceneMoved, keeping the temporal history
+    // (pt_set_scene_moved, rule 7 of pt_hip.h).  previousObject[k] = the index object k had in the last scene's
+    // array, or 0xffffffff for an object that was not there; null: object k was object k, and the counts must then
+    // match.  The per-object maps come from the two scenes' transforms (ptamd::motionRows); the per-primitive table,
+    // with its indices in the last scene's BVH order, is kept (motionRows, motionPrevIndex: one entry per primitive
+    // of the new BVH).  An object whose map is not finite takes no history.  Without an earlier scene the call is
+    // setScene.  One move per temporal step: a second move before the next temporal() ends the history.  Objects
+    // that are word for word the same are told apart by their order in the array.  Single device only.
+    void setSceneMoved(size_t count, const CpuHittable* hittables, const uint32_t* previousObject = nullptr);
+    bool holdsMotion() const;                        // a motion table is held for the next temporal step
+    const std::vector<float>& motionRows() const { return m_motionRows; }
+    const std::vector<uint32_t>& motionPrevIndex() const { return m_motionPrev; }
     void render(const Camera& camera, uint32_t spp, bool ignoreHistory);
     // `chunks` successive render(camera, spp, ...) calls in one launch (first one honours
     // ignoreHistory); bit-identical to the loop.  Timing covers the whole launch.
@@ -321,6 +333,9 @@ public:
     const float* adaptiveVariance();
     float getTiming() const;
     uint32_t loadTexture(const char* path);
+    // While set, loadTexture returns the handle of an already loaded texture with the same size and pixels and
+    // uploads nothing (loadSceneMoved sets it: a texture upload ends the temporal history).
+    void reuseTextures(bool on) { m_reuseTextures = on; }
     void setSkyboxTextureHandle(uint32_t handle);
     float* getHDRImageData();
     char* getImageData();
@@ -358,8 +373,20 @@ private:
     std::vector<float> m_varianceBuffer;
     std::vector<float> m_historyBuffer;
     BVH m_bvh;
+    std::vector<CpuHittable> m_sceneObjects;     // the last scene's objects, in the caller's order
+    std::vector<uint32_t> m_objectToPrim;        // their indices in m_bvh's element order
+    std::vector<float> m_motionRows;             // the last setSceneMoved's table, 12 floats per primitive
+    std::vector<uint32_t> m_motionPrev;
+    struct TextureKey {
+        uint32_t width, height;
+        uint64_t hash;
+    };
+    std::vector<TextureKey> m_textureKeys;       // index = handle - 1
+    bool m_reuseTextures = false;
+    void rememberScene(size_t count, const CpuHittable* hittables);
     void allocHostBuffers();
     void check(int rc, const char* what) const;
+    void refuse(int rc, const char* msg) const;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -385,6 +412,10 @@ struct Params {
 };
 
 Camera loadScene(Pathtracer& pathtracer, const Params& params);
+// loadScene through setSceneMoved: the file's objects against the last scene's (previousObject as there, one entry
+// per object of the file, or null).  A texture of the file whose pixels are already loaded keeps its handle, so an
+// unchanged texture or sky ends nothing; a texture whose pixels changed is uploaded and ends the history as before.
+Camera loadSceneMoved(Pathtracer& pathtracer, const Params& params, const uint32_t* previousObject = nullptr);
 
 namespace ptamd {
 
@@ -406,6 +437,12 @@ bool parseSceneFile(const std::string& path, SceneDesc& out, std::string& error,
                     uint32_t (*textureLoader)(void* user, const std::string& path), void* user);
 
 float radians(float degree);   // SceneLoader.cpp:193-196
+
+// The map of rule 7 (pt_hip.h) for one object from its two world->object transforms (3 x 4 row-major, [A | b]):
+// T = [inverse(A_prev) A_cur | inverse(A_prev) (b_cur - b_prev)], in float64 from the float32 words, rounded once
+// to float32 (the operation order is written out at pth_motion_table, pt_host.h).  False when a word of T is not
+// finite.
+bool motionRows(const float* prevInvRows, const float* curInvRows, float* out);
 
 // Image I/O (stb_image / stb_image_write semantics for the formats the project uses).
 bool isHdrFile(const std::string& path);

@@ -889,6 +889,75 @@ PT_API int pt_despike_image(int device, uint32_t width, uint32_t height, const f
                             const float *plane1, const float *plane2, const pt_despike_params *params, float *out,
                             uint32_t *out_count);
 
+/* ---- Moving objects in the temporal passes --------------------------------------------------------
+ * Rule 3 (temporal reprojection) and rule 4's first part (the step with moments) project one world point with
+ * two cameras: only the camera may move.  Rule 7 is the same step when the objects moved too: a per-primitive
+ * affine map takes a surface point of the current scene to where that object point was in the scene the held
+ * history was made from.  All float32, operation by operation, no contraction, + - x /, floor, compares and
+ * selects only; every dot product as above.  tests/motion_model.py restates it.
+ *
+ * 7. The motion table, one entry per primitive i of the CURRENT scene (prim_count entries, at least 1):
+ *     rows[i]        12 floats, a 3 x 4 row-major affine map T_i (T00 T01 T02 T03 | T10 .. | T20 ..): a world-space
+ *                    point on primitive i now -> the world-space place that object point had in the earlier scene
+ *     prev_index[i]  that primitive's index in the earlier scene, or 0xffffffff: "was not there, take no history
+ *                    for its pixels"
+ *    The table is meant to be rigid (a rotation and a translation).  Nothing checks that: under a scale or a shear
+ *    Nm below is neither unit length nor the normal of the earlier surface, and the plane test's margin, which is
+ *    relative to the current hit distance, no longer measures the earlier geometry.
+ *    Per ok pixel p (rule 3's ok_p), with i = id_p (plane 0's w, as bits):
+ *     i >= prim_count:  the pixel is treated as prev_index == 0xffffffff; the index is clamped (to 0) before the
+ *                       load, as the taps' indices are clamped.  Only the _image forms can meet this.
+ *     Pm.x = ((T00*P.x + T01*P.y) + T02*P.z) + T03,  Pm.y and Pm.z likewise with rows 1 and 2
+ *     Nm.x = (T00*N.x + T01*N.y) + T02*N.z,          Nm.y and Nm.z likewise; Nm is not normalised
+ *     (su0, sv0, z0) = project(cur, P_p);  (su1, sv1, z1) = project(prev, Pm);  fx, fy as in rule 3
+ *     reproj = rule 3's condition && prev_index[i] != 0xffffffff       (a NaN in T_i fails the compares by itself)
+ *     the taps are rule 3's with the moved quantities on the p side: a tap is skipped when  !(w > 0),  or q is
+ *       outside the image,  or n_q < 1,  or a component of I_q is not finite,  or SAME_PRIMITIVE is set and
+ *       id_q != prev_index[i],  or Nm . N_q < normal_cos_min,  or, with g = Nm . (P_q - Pm) and
+ *       m = sigma_plane * t_p,  !(g*g <= m*m)
+ *     everything else is rule 3 unchanged: the weights, the sums, n, the blend, demodulation, the !ok pass-through
+ *     h1 = (N_p, id_p), h2 = (P_p, t_p): the CURRENT scene's words, so the new history is of the current scene
+ *    The moments step (rule 4, part 1) takes the same substitution; its moment sums ride on the same taps, and the
+ *    variance estimate (part 2) reads only the new history and is unchanged.
+ *    With rows = the identity and prev_index[i] = i the words are rule 3's and rule 4's.
+ *    Two kernels of their own, temporal_motion_kernel and temporal_moments_motion_kernel, on the same 32 x 8 tile;
+ *    an entry is four float4 (the rows, then prev_index's bits), read in whole 16-byte loads through the caches.
+ *
+ * Not covered: device groups (pt_group_set_scene is unchanged and ends the history); the command-line tool (a
+ * still has no previous frame); and lighting that a moving object changes on OTHER surfaces -- its shadow, its
+ * bounce light -- which still fades over 1 / alpha_min frames. */
+/* pt_set_scene with a motion table.  Everything pt_set_scene does: the same validation and the same refusals, the
+ * previous scene intact on a refusal.  Also PT_ERR_ARG, naming the primitive, for a prev_index entry that is neither
+ * 0xffffffff nor below the primitive count of the scene it replaces, and for a null table.  The history survives:
+ * "a motion table is held that maps the current scene to the scene of the held history" from this call, made while
+ * a history is held, until the next temporal pass begins (after it the history is of the current scene), a scene
+ * or texture change, or a sky change to another handle.  One move per temporal step: a second pt_set_scene_moved
+ * before the next pass would need the two tables composed, so it ends the history, its moments and the table.
+ * Without a held history the call is pt_set_scene.  The feature planes end as with pt_set_scene. */
+PT_API int pt_set_scene_moved(pt_context *ctx, const pt_bvh_node *nodes, uint32_t node_count, const pt_hittable *prims,
+                              uint32_t prim_count, const float *motion_rows, const uint32_t *prev_index);
+/* 1 while a motion table is held, else 0 (as pt_holds_despiked: a question, never an error).  While it is,
+ * pt_temporal and pt_temporal_moments run rule 7 with the held table (they ask before the pass begins); in every
+ * other case they run exactly what they ran before. */
+PT_API int pt_holds_motion(const pt_context *ctx);
+/* pt_temporal_image and pt_temporal_moments_image under rule 7: their arguments, then the table (motion_rows =
+ * prim_count x 12 floats, prev_index = prim_count words; prim_count 1 .. 2^26 - 1).  prev_index is not checked
+ * against anything: it is only compared with the history's ids.  For gathered frames and tests. */
+PT_API int pt_temporal_motion_image(int device, uint32_t width, uint32_t height, const float *color, const float *plane0,
+                                    const float *plane1, const float *plane2, const pt_camera *cur_cam,
+                                    const float *hist0, const float *hist1, const float *hist2,
+                                    const pt_camera *prev_cam, const pt_temporal_params *params, float *out_image,
+                                    float *out_hist0, float *out_hist1, float *out_hist2, uint32_t prim_count,
+                                    const float *motion_rows, const uint32_t *prev_index);
+PT_API int pt_temporal_moments_motion_image(int device, uint32_t width, uint32_t height, const float *color,
+                                            const float *plane0, const float *plane1, const float *plane2,
+                                            const pt_camera *cur_cam, const float *hist0, const float *hist1,
+                                            const float *hist2, const float *hist3, const pt_camera *prev_cam,
+                                            const pt_temporal_params *params, const pt_variance_params *variance,
+                                            float *out_image, float *out_hist0, float *out_hist1, float *out_hist2,
+                                            float *out_hist3, float *out_variance, uint32_t prim_count,
+                                            const float *motion_rows, const uint32_t *prev_index);
+
 /* ---- Multi-device group (one process, one context per GPU, RCCL over xGMI) -------------------
  * Replaces the reference's hard-coded single device (Pathtracer.cpp:40: cudaSetDevice(0)) behind
  * the same Pathtracer interface: device i renders the row bands b = i, i + N, ... of the image

@@ -69,6 +69,35 @@ PT_API float pth_renderer_gather_ms(const pth_renderer *r);
 PT_API void pth_renderer_destroy(pth_renderer *r);
 /* loadScene(pathtracer, params) for a scene file; fills the camera (aspect = width / height). */
 PT_API int pth_renderer_load_scene(pth_renderer *r, const char *path, pt_camera *camera);
+/* loadSceneMoved / Pathtracer::setSceneMoved for a scene file whose objects moved since the renderer's last scene:
+ * the temporal history survives and the next pth_renderer_temporal / _temporal_moments reprojects through the
+ * objects' motion (pt_set_scene_moved, rule 7 of pt_hip.h; single device).  previous_object: one entry per object
+ * of the file, the index that object had in the last scene's file order or 0xffffffff for a new one; NULL: object
+ * k was object k, and PT_ERR_ARG naming both counts when they differ.  The renderer keeps the last scene's objects
+ * and where its BVH put them; it builds the new BVH, turns the correspondences into the per-primitive table with
+ * prev_index in the last BVH's order, and calls pt_set_scene_moved.  A texture of the file whose pixels are already
+ * loaded keeps its handle (so an unchanged texture or sky ends nothing); one whose pixels changed is uploaded and
+ * ends the history.  Without an earlier scene the call is pth_renderer_load_scene.  One move per temporal step: a
+ * second call before the next temporal step ends the history.
+ * pth_renderer_holds_motion: pt_holds_motion.  pth_renderer_motion_table: the table of the last successful move
+ * (borrowed pointers, valid until the next scene call; returns the primitive count, 0 when there is none). */
+PT_API int pth_renderer_load_scene_moved(pth_renderer *r, const char *path, const uint32_t *previous_object,
+                                         pt_camera *camera);
+PT_API int pth_renderer_holds_motion(const pth_renderer *r);
+PT_API uint32_t pth_renderer_motion_table(const pth_renderer *r, const float **rows, const uint32_t **prev_index);
+/* Rule 7's map for `count` objects from their records in two scenes; pure CPU, no HIP call.  With the world->object
+ * rows [A | b] of prev[i] and cur[i] (inv_transform_rows), T_i = [inverse(A_prev) A_cur | inverse(A_prev) (b_cur -
+ * b_prev)] takes a world point on the object now to where that object point was.  Computed in float64 from the
+ * float32 words, in exactly these operations (tests/motion_model.py restates them), a = A_prev, c = A_cur:
+ *   cofactors  C00 = a11*a22 - a12*a21   C01 = a12*a20 - a10*a22   C02 = a10*a21 - a11*a20
+ *              C10 = a02*a21 - a01*a22   C11 = a00*a22 - a02*a20   C12 = a01*a20 - a00*a21
+ *              C20 = a01*a12 - a02*a11   C21 = a02*a10 - a00*a12   C22 = a00*a11 - a01*a10
+ *   det = (a00*C00 + a01*C01) + a02*C02;   inv[r][k] = C[k][r] / det          (one division per element)
+ *   T[r][k] = (inv[r][0]*c[0][k] + inv[r][1]*c[1][k]) + inv[r][2]*c[2][k]      for k = 0..2, summed left to right
+ *   d[k] = b_cur[k] - b_prev[k];   T[r][3] = (inv[r][0]*d[0] + inv[r][1]*d[1]) + inv[r][2]*d[2]
+ * each T word rounded once to float32.  rows = count x 12 floats; valid[i] = 1, or 0 when a word of T_i is not
+ * finite: the caller then sets prev_index = 0xffffffff for it. */
+PT_API int pth_motion_table(const pt_hittable *prev, const pt_hittable *cur, uint32_t count, float *rows, uint32_t *valid);
 /* `chunks` x Pathtracer::render(camera, spp, ignore_history && first) in one launch. */
 PT_API int pth_renderer_render(pth_renderer *r, const pt_camera *camera, uint32_t spp, uint32_t chunks, int ignore_history);
 /* Pathtracer::renderAdaptive (pt_render_adaptive, pt_hip.h; single device).  Afterwards

@@ -31,7 +31,7 @@ __all__ = ["Pathtracer", "Scene", "make_camera", "camera_rotate", "camera_transl
            "temporal_moments_image", "denoise_variance_image", "VARIANCE_DEFAULTS", "VDENOISE_DEFAULTS",
            "vfeedback_params", "denoise_variance_feedback_image", "VFEEDBACK_DEFAULTS", "adaptive_variance_params",
            "adaptive_variance_image", "AVARIANCE_DEFAULTS", "ADENOISE_SIGMA_L", "despike_params", "despike_image",
-           "DESPIKE_DEFAULTS"]
+           "DESPIKE_DEFAULTS", "motion_table", "temporal_motion_image", "temporal_moments_motion_image", "NO_PREVIOUS"]
 
 HITTABLE_TYPES = ["SPHERE", "CYLINDER", "DISK", "CONE", "PARABOLOID", "QUAD", "CUBE"]   # Hittable.h:9-12
 MATERIAL_TYPES = ["LAMBERT", "GGX", "LAMBERT_GGX"]                                     # Material.h:9-12
@@ -228,6 +228,104 @@ def temporal_image(color, plane0, plane1, plane2, cur_camera: PtCamera, history=
     rc = N.hip().pt_temporal_image(int(device), c.shape[1], c.shape[0], *[a.ctypes.data_as(fp) for a in arrays],
                                    C.byref(cur_camera), *hp, C.byref(prev_camera) if prev_camera is not None else None,
                                    C.byref(params), *[o.ctypes.data_as(fp) for o in outs])
+    N.check_ctx(rc, None)
+    return tuple(outs)
+
+
+NO_PREVIOUS = 0xffffffff     # prev_index / previous-object entry of something that was not in the earlier scene
+
+
+def motion_table(prev_objects, cur_objects):
+    """pth_motion_table: rule 7's per-object maps (include/pt_hip.h, include/pt_host.h) from two equally long
+    sequences of PtHittable -- object i as it was and as it is.  Pure CPU.  Returns (rows, valid): count x 3 x 4
+    float32 and count bool; an entry that is not valid (a word of its map is not finite) must get NO_PREVIOUS as its
+    prev_index."""
+    prev, cur = list(prev_objects), list(cur_objects)
+    if len(prev) != len(cur):
+        raise _refuse(f"motion_table: {len(prev)} previous objects and {len(cur)} current ones")
+    n = len(cur)
+    rows = np.zeros((n, 3, 4), dtype=np.float32)
+    valid = np.zeros(n, dtype=np.uint32)
+    if n:
+        N.check_host(N.host().pth_motion_table((PtHittable * n)(*prev), (PtHittable * n)(*cur), n,
+                                               rows.ctypes.data_as(C.POINTER(C.c_float)),
+                                               valid.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return rows, valid != 0
+
+
+def _motion_arrays(what: str, motion_rows, prev_index):
+    rows = np.ascontiguousarray(motion_rows, dtype=np.float32)
+    prev = np.ascontiguousarray(prev_index, dtype=np.uint32)
+    if rows.ndim < 1 or rows.size != 12 * prev.size or prev.ndim != 1:
+        raise _refuse(f"{what}: motion_rows must be count x 3 x 4 and prev_index count, not {rows.shape} and {prev.shape}")
+    return rows, prev
+
+
+def temporal_motion_image(color, plane0, plane1, plane2, cur_camera: PtCamera, motion_rows, prev_index, history=None,
+                          prev_camera: Optional[PtCamera] = None, alpha_min: Optional[float] = None,
+                          max_history: Optional[int] = None, sigma_plane: Optional[float] = None,
+                          normal_cos_min: Optional[float] = None, demodulate: Optional[bool] = None,
+                          same_primitive: Optional[bool] = None, device: int = 0):
+    """pt_temporal_motion_image: temporal_image() under rule 7 of include/pt_hip.h.  motion_rows (count x 3 x 4
+    float32) and prev_index (count uint32, NO_PREVIOUS = take no history) have one entry per primitive of the scene
+    the planes were made from: the map to, and the index in, the scene `history` was made from.  Returns (image, h0,
+    h1, h2); the new history is of the current scene."""
+    params = temporal_params(alpha_min, max_history, sigma_plane, normal_cos_min, demodulate, same_primitive)
+    rows, prev = _motion_arrays("temporal_motion_image", motion_rows, prev_index)
+    c = _image4("color", color)
+    arrays = [c] + [_image4(f"plane{k}", p, c.shape) for k, p in enumerate((plane0, plane1, plane2))]
+    fp = C.POINTER(C.c_float)
+    null = C.cast(None, fp)
+    if history is not None:
+        if prev_camera is None:
+            raise _refuse("temporal_motion_image: history is given without prev_camera")
+        hist = [_image4(f"history[{k}]", h, c.shape) for k, h in enumerate(history)]
+        if len(hist) != 3:
+            raise _refuse("temporal_motion_image: history must be (h0, h1, h2)")
+        hp = [h.ctypes.data_as(fp) for h in hist]
+    else:
+        hp = [null, null, null]
+    outs = [np.zeros_like(c) for _ in range(4)]
+    rc = N.hip().pt_temporal_motion_image(int(device), c.shape[1], c.shape[0], *[a.ctypes.data_as(fp) for a in arrays],
+                                          C.byref(cur_camera), *hp,
+                                          C.byref(prev_camera) if prev_camera is not None else None, C.byref(params),
+                                          *[o.ctypes.data_as(fp) for o in outs], int(prev.size), rows.ctypes.data_as(fp),
+                                          prev.ctypes.data_as(C.POINTER(C.c_uint32)))
+    N.check_ctx(rc, None)
+    return tuple(outs)
+
+
+def temporal_moments_motion_image(color, plane0, plane1, plane2, cur_camera: PtCamera, motion_rows, prev_index,
+                                  history=None, prev_camera: Optional[PtCamera] = None, alpha_min: Optional[float] = None,
+                                  max_history: Optional[int] = None, sigma_plane: Optional[float] = None,
+                                  normal_cos_min: Optional[float] = None, demodulate: Optional[bool] = None,
+                                  same_primitive: Optional[bool] = None, min_temporal: Optional[int] = None,
+                                  device: int = 0):
+    """pt_temporal_moments_motion_image: temporal_moments_image() under rule 7 (see temporal_motion_image).
+    Returns (image, h0, h1, h2, h3, variance)."""
+    params = temporal_params(alpha_min, max_history, sigma_plane, normal_cos_min, demodulate, same_primitive)
+    vparams = variance_params(min_temporal)
+    rows, prev = _motion_arrays("temporal_moments_motion_image", motion_rows, prev_index)
+    c = _image4("color", color)
+    arrays = [c] + [_image4(f"plane{k}", p, c.shape) for k, p in enumerate((plane0, plane1, plane2))]
+    fp = C.POINTER(C.c_float)
+    null = C.cast(None, fp)
+    if history is not None:
+        if prev_camera is None:
+            raise _refuse("temporal_moments_motion_image: history is given without prev_camera")
+        hist = [_image4(f"history[{k}]", h, c.shape) for k, h in enumerate(history)]
+        if len(hist) != 4:
+            raise _refuse("temporal_moments_motion_image: history must be (h0, h1, h2, h3)")
+        hp = [h.ctypes.data_as(fp) for h in hist]
+    else:
+        hp = [null, null, null, null]
+    outs = [np.zeros_like(c) for _ in range(5)] + [np.zeros(c.shape[:2], dtype=np.float32)]
+    rc = N.hip().pt_temporal_moments_motion_image(int(device), c.shape[1], c.shape[0],
+                                                  *[a.ctypes.data_as(fp) for a in arrays], C.byref(cur_camera), *hp,
+                                                  C.byref(prev_camera) if prev_camera is not None else None,
+                                                  C.byref(params), C.byref(vparams), *[o.ctypes.data_as(fp) for o in outs],
+                                                  int(prev.size), rows.ctypes.data_as(fp),
+                                                  prev.ctypes.data_as(C.POINTER(C.c_uint32)))
     N.check_ctx(rc, None)
     return tuple(outs)
 
@@ -654,6 +752,42 @@ class Pathtracer:
         cam = PtCamera()
         N.check_host(N.host().pth_renderer_load_scene(self._r, os.fsencode(str(path)), C.byref(cam)))
         return cam
+
+    def load_scene_moved(self, path: str, previous: Optional[Sequence[int]] = None) -> PtCamera:
+        """load_scene() for a file whose objects moved since the last load, keeping the temporal history
+        (pth_renderer_load_scene_moved; rule 7 of include/pt_hip.h): the next temporal() reprojects every pixel
+        through its object's motion.  previous[k] = the index object k of the file had in the last scene's file, or
+        NO_PREVIOUS for a new object; None: object k was object k (the counts must then match).  Per frame:
+        load_scene_moved(f_k), render(cam, 1, True), features(cam), temporal(variance=True),
+        denoise(source="temporal", guide="variance").  One move per temporal step: a second move before the next
+        temporal() ends the history.  Single device only."""
+        self._single("load_scene_moved")
+        cam = PtCamera()
+        prev = None
+        if previous is not None:
+            prev = np.ascontiguousarray([int(v) for v in previous], dtype=np.uint32)
+            n = int(Scene(str(path), self.width, self.height).object_count)
+            if prev.size != n:
+                raise _refuse(f"load_scene_moved: previous has {prev.size} entries, the scene {n} objects")
+        N.check_host(N.host().pth_renderer_load_scene_moved(
+            self._r, os.fsencode(str(path)), prev.ctypes.data_as(C.POINTER(C.c_uint32)) if prev is not None else None,
+            C.byref(cam)))
+        return cam
+
+    def holds_motion(self) -> bool:
+        """Whether a motion table is held for the next temporal step (pt_holds_motion): from a load_scene_moved over a
+        held history until the next temporal(), load_scene, texture or other sky."""
+        self._single("holds_motion")
+        return bool(N.hip().pt_holds_motion(self._ctx))
+
+    def motion_table(self):
+        """The per-primitive table of the last load_scene_moved (rows: count x 3 x 4 float32, prev_index: count
+        uint32, in the current BVH's primitive order), or None when the last scene call was not a move."""
+        rows, prev = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)()
+        n = int(N.host().pth_renderer_motion_table(self._r, C.byref(rows), C.byref(prev)))
+        if n == 0:
+            return None
+        return (np.ctypeslib.as_array(rows, shape=(n, 3, 4)).copy(), np.ctypeslib.as_array(prev, shape=(n,)).copy())
 
     def render(self, camera: PtCamera, spp: int, ignore_history: bool, chunks: int = 1) -> None:
         """`chunks` x render(camera, spp, ignore_history and first) in one kernel launch."""

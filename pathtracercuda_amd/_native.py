@@ -206,6 +206,15 @@ _HIP_SYMBOLS = {
     "pt_denoise_despiked": (C.c_int, [C.c_void_p, P(PtDenoiseParams)]),
     "pt_despike_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 4
                          + [P(PtDespikeParams), P(C.c_float), P(C.c_uint32)]),
+    "pt_set_scene_moved": (C.c_int, [C.c_void_p, P(PtBvhNode), C.c_uint32, P(PtHittable), C.c_uint32, P(C.c_float),
+                                     P(C.c_uint32)]),
+    "pt_holds_motion": (C.c_int, [C.c_void_p]),
+    "pt_temporal_motion_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 4 + [P(PtCamera)]
+                                 + [P(C.c_float)] * 3 + [P(PtCamera), P(PtTemporalParams)] + [P(C.c_float)] * 4
+                                 + [C.c_uint32, P(C.c_float), P(C.c_uint32)]),
+    "pt_temporal_moments_motion_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 4 + [P(PtCamera)]
+                                         + [P(C.c_float)] * 4 + [P(PtCamera), P(PtTemporalParams), P(PtVarianceParams)]
+                                         + [P(C.c_float)] * 6 + [C.c_uint32, P(C.c_float), P(C.c_uint32)]),
     "pt_group_create": (C.c_int, [C.c_int, P(C.c_int), C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_void_p)]),
     "pt_group_destroy": (None, [C.c_void_p]),
     "pt_group_size": (C.c_int, [C.c_void_p]),
@@ -246,6 +255,10 @@ _HOST_SYMBOLS = {
     "pth_renderer_gather_ms": (C.c_float, [C.c_void_p]),
     "pth_renderer_destroy": (None, [C.c_void_p]),
     "pth_renderer_load_scene": (C.c_int, [C.c_void_p, C.c_char_p, P(PtCamera)]),
+    "pth_renderer_load_scene_moved": (C.c_int, [C.c_void_p, C.c_char_p, P(C.c_uint32), P(PtCamera)]),
+    "pth_renderer_holds_motion": (C.c_int, [C.c_void_p]),
+    "pth_renderer_motion_table": (C.c_uint32, [C.c_void_p, P(P(C.c_float)), P(P(C.c_uint32))]),
+    "pth_motion_table": (C.c_int, [P(PtHittable), P(PtHittable), C.c_uint32, P(C.c_float), P(C.c_uint32)]),
     "pth_renderer_render": (C.c_int, [C.c_void_p, P(PtCamera), C.c_uint32, C.c_uint32, C.c_int]),
     "pth_renderer_render_adaptive": (C.c_int, [C.c_void_p, P(PtCamera), P(PtAdaptiveParams), P(PtAdaptiveResult)]),
     "pth_renderer_adaptive": (C.c_int, [C.c_void_p]),

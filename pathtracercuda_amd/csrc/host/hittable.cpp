@@ -134,3 +134,41 @@ pt_hittable CpuHittable::getGpuHittable() const
     h.type = (uint32_t)m_type;
     return h;
 }
+
+namespace ptamd {
+
+bool motionRows(const float* prevInvRows, const float* curInvRows, float* out)
+{
+    double a[3][4], c[3][4];
+    for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 4; ++k) {
+            a[r][k] = (double)prevInvRows[4 * r + k];
+            c[r][k] = (double)curInvRows[4 * r + k];
+        }
+    // cofactors of A_prev; the inverse is their transpose over the determinant, one division per element
+    double co[3][3];
+    co[0][0] = a[1][1] * a[2][2] - a[1][2] * a[2][1];
+    co[0][1] = a[1][2] * a[2][0] - a[1][0] * a[2][2];
+    co[0][2] = a[1][0] * a[2][1] - a[1][1] * a[2][0];
+    co[1][0] = a[0][2] * a[2][1] - a[0][1] * a[2][2];
+    co[1][1] = a[0][0] * a[2][2] - a[0][2] * a[2][0];
+    co[1][2] = a[0][1] * a[2][0] - a[0][0] * a[2][1];
+    co[2][0] = a[0][1] * a[1][2] - a[0][2] * a[1][1];
+    co[2][1] = a[0][2] * a[1][0] - a[0][0] * a[1][2];
+    co[2][2] = a[0][0] * a[1][1] - a[0][1] * a[1][0];
+    const double det = (a[0][0] * co[0][0] + a[0][1] * co[0][1]) + a[0][2] * co[0][2];
+    double inv[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 3; ++k) inv[r][k] = co[k][r] / det;
+    const double d[3] = {c[0][3] - a[0][3], c[1][3] - a[1][3], c[2][3] - a[2][3]};
+    bool finite = true;
+    for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k)
+            out[4 * r + k] = (float)((inv[r][0] * c[0][k] + inv[r][1] * c[1][k]) + inv[r][2] * c[2][k]);
+        out[4 * r + 3] = (float)((inv[r][0] * d[0] + inv[r][1] * d[1]) + inv[r][2] * d[2]);
+        for (int k = 0; k < 4; ++k) finite = finite && std::isfinite(out[4 * r + k]);
+    }
+    return finite;
+}
+
+} // namespace ptamd

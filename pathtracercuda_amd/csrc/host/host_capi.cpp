@@ -276,6 +276,44 @@ PT_API int pth_renderer_load_scene(pth_renderer* r, const char* path, pt_camera*
     PTH_GUARD_END
 }
 
+PT_API int pth_renderer_load_scene_moved(pth_renderer* r, const char* path, const uint32_t* previous_object, pt_camera* camera)
+{
+    if (!r || !path) return setError(PT_ERR_ARG, "invalid argument");
+    PTH_GUARD_BEGIN
+    Params p;
+    p.m_width = r->pt->width();
+    p.m_height = r->pt->height();
+    p.m_inputFilepath = path;
+    ptamd::SceneDesc probe;
+    std::string err;
+    if (!ptamd::parseSceneFile(path, probe, err, nullptr, nullptr)) return setError(PT_ERR_ARG, err);
+    const Camera cam = loadSceneMoved(*r->pt, p, previous_object);
+    if (camera) *camera = cam.toDevice();
+    return PT_OK;
+    PTH_GUARD_END
+}
+
+PT_API int pth_renderer_holds_motion(const pth_renderer* r) { return r && r->pt->holdsMotion() ? 1 : 0; }
+
+PT_API uint32_t pth_renderer_motion_table(const pth_renderer* r, const float** rows, const uint32_t** prev_index)
+{
+    if (rows) *rows = nullptr;
+    if (prev_index) *prev_index = nullptr;
+    if (!r) return 0;
+    const uint32_t n = (uint32_t)r->pt->motionPrevIndex().size();
+    if (rows && n) *rows = r->pt->motionRows().data();
+    if (prev_index && n) *prev_index = r->pt->motionPrevIndex().data();
+    return n;
+}
+
+PT_API int pth_motion_table(const pt_hittable* prev, const pt_hittable* cur, uint32_t count, float* rows, uint32_t* valid)
+{
+    if (count && (!prev || !cur || !rows || !valid)) return setError(PT_ERR_ARG, "pth_motion_table: an array is null");
+    for (uint32_t i = 0; i < count; ++i)
+        valid[i] = ptamd::motionRows(&prev[i].inv_transform_rows[0][0], &cur[i].inv_transform_rows[0][0], rows + 12 * (size_t)i) ? 1u : 0u;
+    return PT_OK;
+}
+
 PT_API int pth_renderer_render(pth_renderer* r, const pt_camera* camera, uint32_t spp, uint32_t chunks, int ignore_history)
 {
     if (!r || !camera) return setError(PT_ERR_ARG, "invalid argument");

@@ -7,7 +7,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "host_internal.h"
@@ -26,6 +28,14 @@ void Pathtracer::check(int rc, const char* what) const
     if (ptamd::g_throwOnError) throw ptamd::Error(rc, buf);
     // reference behaviour (Pathtracer.cpp:17-28): report and terminate
     fprintf(stderr, "%s\n", buf);
+    exit(EXIT_FAILURE);
+}
+
+// a refusal of this class's own, before any device call
+void Pathtracer::refuse(int rc, const char* msg) const
+{
+    if (ptamd::g_throwOnError) throw ptamd::Error(rc, msg);
+    fprintf(stderr, "%s\n", msg);
     exit(EXIT_FAILURE);
 }
 
@@ -101,7 +111,105 @@ void Pathtracer::setScene(size_t count, const CpuHittable* hittables)
     m_hittableCount = (uint32_t)dp.size();
     m_denoised = false;
     m_despiked = false;
+    rememberScene(count, hittables);
+    m_motionRows.clear();
+    m_motionPrev.clear();
 }
+
+// The objects in the caller's order, and where BVH::build put each: an element is matched to the first object
+// not yet taken whose device record is the same words (objects that are word for word the same are interchangeable
+// to the tracer; taking them in order keeps the match deterministic).
+void Pathtracer::rememberScene(size_t count, const CpuHittable* hittables)
+{
+    std::vector<CpuHittable> objects(hittables, hittables + count);   // (hittables may point into m_sceneObjects)
+    const auto key = [](const CpuHittable& h) {
+        const pt_hittable g = h.getGpuHittable();
+        return std::string((const char*)&g, sizeof(g));
+    };
+    std::map<std::string, std::vector<uint32_t>> byWords;
+    for (size_t k = count; k-- > 0;) byWords[key(objects[k])].push_back((uint32_t)k);   // popped from the back: in order
+    const auto& elems = m_bvh.getElements();
+    m_objectToPrim.assign(count, 0xffffffffu);
+    for (size_t p = 0; p < elems.size(); ++p) {
+        auto it = byWords.find(key(elems[p]));
+        if (it == byWords.end() || it->second.empty()) check(PT_ERR_STATE, "setScene: a BVH element matches no object");
+        m_objectToPrim[it->second.back()] = (uint32_t)p;
+        it->second.pop_back();
+    }
+    m_sceneObjects.swap(objects);
+}
+
+void Pathtracer::setSceneMoved(size_t count, const CpuHittable* hittables, const uint32_t* previousObject)
+{
+    if (m_group) check(PT_ERR_STATE, "setSceneMoved: not available on a device group");
+    if (count == 0) {
+        printf("Setting an empty scene is not allowed!\n");
+        return;
+    }
+    if (m_sceneObjects.empty()) {       // nothing to move from
+        setScene(count, hittables);
+        return;
+    }
+    const size_t prevCount = m_sceneObjects.size();
+    char msg[200];
+    if (!previousObject && count != prevCount) {
+        snprintf(msg, sizeof(msg), "setSceneMoved: the scene has %zu objects and the previous one %zu "
+                 "(give previousObject when the counts differ)", count, prevCount);
+        refuse(PT_ERR_ARG, msg);
+    }
+    for (size_t k = 0; previousObject && k < count; ++k)
+        if (previousObject[k] != 0xffffffffu && previousObject[k] >= prevCount) {
+            snprintf(msg, sizeof(msg), "setSceneMoved: previousObject[%zu] = %u is neither 0xffffffff nor below the "
+                     "previous scene's %zu objects", k, previousObject[k], prevCount);
+            refuse(PT_ERR_ARG, msg);
+        }
+    // per object: the map and the primitive it was in the previous BVH
+    std::vector<float> objRows(12 * count, 0.0f);
+    std::vector<uint32_t> objPrev(count, 0xffffffffu);
+    for (size_t k = 0; k < count; ++k) {
+        const uint32_t j = previousObject ? previousObject[k] : (uint32_t)k;
+        if (j == 0xffffffffu) continue;
+        if (ptamd::motionRows(m_sceneObjects[j].invTransformRows(), hittables[k].invTransformRows(), &objRows[12 * k]))
+            objPrev[k] = m_objectToPrim[j];
+    }
+    BVH bvh;
+    bvh.build(count, hittables, 4);
+    if (!bvh.validate()) check(PT_ERR_STATE, "BVH::validate");
+    const BVH before = m_bvh;
+    const std::vector<CpuHittable> objectsBefore = m_sceneObjects;
+    const std::vector<uint32_t> permBefore = m_objectToPrim;
+    m_bvh = bvh;
+    rememberScene(count, hittables);
+    const auto& nodes = m_bvh.getNodes();
+    const auto& elems = m_bvh.getElements();
+    std::vector<pt_bvh_node> dn(nodes.size());
+    for (size_t i = 0; i < nodes.size(); ++i) dn[i] = ptamd::toDeviceNode(nodes[i]);
+    std::vector<pt_hittable> dp(elems.size());
+    for (size_t i = 0; i < elems.size(); ++i) dp[i] = elems[i].getGpuHittable();
+    std::vector<float> rows(12 * elems.size());
+    std::vector<uint32_t> prev(elems.size());
+    for (size_t k = 0; k < count; ++k) {
+        const uint32_t p = m_objectToPrim[k];
+        memcpy(&rows[12 * (size_t)p], &objRows[12 * k], 12 * sizeof(float));
+        prev[p] = objPrev[k];
+    }
+    const int rc = pt_set_scene_moved(m_ctx, dn.data(), (uint32_t)dn.size(), dp.data(), (uint32_t)dp.size(), rows.data(),
+                                      prev.data());
+    if (rc != PT_OK) {                  // refused: the device keeps the previous scene, and so does this class
+        m_bvh = before;
+        m_sceneObjects = objectsBefore;
+        m_objectToPrim = permBefore;
+        check(rc, "pt_set_scene_moved");
+    }
+    m_motionRows.swap(rows);
+    m_motionPrev.swap(prev);
+    m_nodeCount = (uint32_t)dn.size();
+    m_hittableCount = (uint32_t)dp.size();
+    m_denoised = false;
+    m_despiked = false;
+}
+
+bool Pathtracer::holdsMotion() const { return !m_group && pt_holds_motion(m_ctx) != 0; }
 
 void Pathtracer::render(const Camera& camera, uint32_t spp, bool ignoreHistory)
 {
@@ -327,9 +435,26 @@ uint32_t Pathtracer::loadTexture(const char* path)
     uint32_t w = 0, h = 0;
     std::string err;
     if (!ptamd::loadImageRGBA32F(path, rgba, w, h, err)) return 0;     // failure -> null handle
+    uint64_t hash = 1469598103934665603ull;                            // FNV-1a over the pixel words
+    for (const float v : rgba) {
+        uint32_t u;
+        memcpy(&u, &v, 4);
+        for (int k = 0; k < 4; ++k) hash = (hash ^ ((u >> (8 * k)) & 0xffu)) * 1099511628211ull;
+    }
+    if (m_reuseTextures) {
+        // the sky's own handle first (only that one leaves the sky as it is), then the latest load with these pixels
+        const auto same = [&](size_t i) {
+            return m_textureKeys[i].width == w && m_textureKeys[i].height == h && m_textureKeys[i].hash == hash;
+        };
+        if (m_skyboxTextureHandle >= 1 && m_skyboxTextureHandle <= m_textureKeys.size() && same(m_skyboxTextureHandle - 1))
+            return m_skyboxTextureHandle;
+        for (size_t i = m_textureKeys.size(); i-- > 0;)
+            if (same(i)) return (uint32_t)i + 1;
+    }
     if (m_group) check(pt_group_set_texture(m_group, m_textureCount + 1, rgba.data(), w, h), "pt_group_set_texture");
     else check(pt_set_texture(m_ctx, m_textureCount + 1, rgba.data(), w, h), "pt_set_texture");
     ++m_textureCount;
+    m_textureKeys.push_back({w, h, hash});
     m_despiked = false;
     return m_textureCount;
 }

@@ -199,3 +199,21 @@ Camera loadScene(Pathtracer& pathtracer, const Params& params)
     return Camera(desc.cameraPosition, desc.cameraLookAt, vec3(0.0f, 1.0f, 0.0f), ptamd::radians(desc.cameraFovyDegrees),
                   (float)params.m_width / params.m_height);
 }
+
+Camera loadSceneMoved(Pathtracer& pathtracer, const Params& params, const uint32_t* previousObject)
+{
+    ptamd::SceneDesc desc;
+    std::string error;
+    LoadCtx ctx{&pathtracer, params.m_inputFilepath ? params.m_inputFilepath : ""};
+    pathtracer.reuseTextures(true);
+    const bool parsed = ptamd::parseSceneFile(ctx.scenePath, desc, error, loadTextureCb, &ctx);
+    pathtracer.reuseTextures(false);
+    if (!parsed) {
+        printf("%s\n", error.c_str());
+        exit(EXIT_FAILURE);
+    }
+    if (desc.hasObjects) pathtracer.setSceneMoved(desc.objects.size(), desc.objects.data(), previousObject);
+    if (desc.hasSkybox) pathtracer.setSkyboxTextureHandle(desc.skyboxHandle);
+    return Camera(desc.cameraPosition, desc.cameraLookAt, vec3(0.0f, 1.0f, 0.0f), ptamd::radians(desc.cameraFovyDegrees),
+                  (float)params.m_width / params.m_height);
+}

@@ -48,6 +48,13 @@
 //                   beginning, by a launch that writes the accumulation (a render, an adaptive render), by the
 //                   beginning of a features call, by a scene or texture change and by a sky change to another handle.
 //                   An RNG write and a camera change end nothing: neither touches the image or the planes.
+//   motionValid     "a motion table is held that maps the current scene to the scene of the held history" (rule 7 of
+//                   include/pt_hip.h; pt_holds_motion, and pt_temporal / pt_temporal_moments run the motion kernels
+//                   while it holds): set by scene_moved over a held history, ended by the beginning of a temporal pass
+//                   (after it the history is of the current scene, or there is none), by a scene or texture change,
+//                   by a sky change to another handle, and by a second scene_moved (one move per temporal step: the
+//                   two tables would have to be composed, so the history ends with it).  A render, a camera change,
+//                   an RNG write and a features call end nothing.  Implies histValid.
 //   epoch           counts the launches that wrote the accumulation (a device group's gather cache
 //                   key, pt_group.h).  Never decreases.
 // A call refused for its arguments or for the state raises no event (but for a render whose plan is a
@@ -73,6 +80,7 @@ struct CtxState {
     bool momValid = false;
     bool avValid = false;
     bool dsValid = false;
+    bool motionValid = false;
     uint64_t epoch = 0;
 };
 
@@ -86,7 +94,20 @@ inline void scene_or_texture_changed(CtxState& s)
     s.histValid = false;
     s.momValid = false;
     s.dsValid = false;
+    s.motionValid = false;
     ++s.stateEpoch;
+}
+
+// pt_set_scene_moved: a scene change that comes with a motion table.  The history and its moments survive the first
+// move after a temporal pass and the table is held beside them; a second move before the next pass ends all three
+// (one move per temporal step).  Everything else is scene_or_texture_changed's.
+inline void scene_moved(CtxState& s)
+{
+    const bool hist = s.histValid && !s.motionValid, mom = s.momValid && !s.motionValid;
+    scene_or_texture_changed(s);
+    s.histValid = hist;
+    s.momValid = mom;
+    s.motionValid = hist;
 }
 
 // pt_set_skybox while `held` is set: only another handle changes anything (the planes hold first hits: no
@@ -99,6 +120,7 @@ inline void sky_set(CtxState& s, uint32_t held, uint32_t handle)
     s.histValid = false;
     s.momValid = false;
     s.dsValid = false;
+    s.motionValid = false;
 }
 
 // pt_write_rng: a stash and the moments continue the old streams
@@ -197,6 +219,7 @@ inline void temporal_begins(CtxState& s)
     s.histValid = false;
     s.tpOfPlanes = false;
     s.momValid = false;
+    s.motionValid = false;
 }
 inline void temporal_done(CtxState& s)
 {
@@ -224,5 +247,6 @@ inline bool temporal_of_planes(const CtxState& s) { return s.tpOfPlanes; }
 inline bool history_has_moments(const CtxState& s) { return s.momValid; }
 inline bool variance_of_counts(const CtxState& s) { return s.avValid; }
 inline bool holds_despiked(const CtxState& s) { return s.dsValid; }
+inline bool holds_motion(const CtxState& s) { return s.motionValid; }
 
 } // namespace pt

@@ -110,6 +110,106 @@ __global__ void __launch_bounds__(256) temporal_moments_kernel(MomentsArgs M)
     M.h3[pi] = make_float4(m1, m2, sv_clamp0(m2 - m1 * m1), 0.0f);
 }
 
+// The same step under rule 7 (pt_dev_temporal.h): temporal_motion_kernel's substitution on the p side of the
+// taps, the moment sums riding on the same taps.  Again a kernel of its own.
+struct MomentsMotionArgs {
+    MomentsArgs M;
+    MotionTable motion;         // read only where M.T.ph0 is set
+};
+
+__global__ void __launch_bounds__(256) temporal_moments_motion_kernel(MomentsMotionArgs B)
+{
+    const MomentsArgs& M = B.M;
+    const TemporalArgs& A = M.T;
+    const uint32_t lx = threadIdx.x & (kDnTileW - 1u), ly = threadIdx.x / kDnTileW;
+    const uint32_t x = blockIdx.x * kDnTileW + lx, y = blockIdx.y * kDnTileH + ly;
+    if (x >= A.width || y >= A.height) return;
+    const size_t pi = (size_t)y * A.width + x;
+    const float4 c = A.color[pi], a = A.plane0[pi], n4 = A.plane1[pi], p4 = A.plane2[pi];
+    A.h1[pi] = make_float4(n4.x, n4.y, n4.z, a.w);
+    A.h2[pi] = make_float4(p4.x, p4.y, p4.z, n4.w);
+    const bool ok = (__float_as_uint(p4.w) & PT_FEATURE_HIT) && dn_finite(c.x) && dn_finite(c.y) && dn_finite(c.z) &&
+                    dn_finite(n4.x) && dn_finite(n4.y) && dn_finite(n4.z) && dn_finite(p4.x) && dn_finite(p4.y) &&
+                    dn_finite(p4.z);
+    if (!ok) {
+        const float4 o = make_float4(c.x, c.y, c.z, 0.0f);
+        A.image[pi] = o;
+        A.h0[pi] = o;
+        M.h3[pi] = make_float4(0.0f, 0.0f, -1.0f, 0.0f);
+        return;
+    }
+    const f3 D = dn_divisor(a, (A.flags & PT_TEMPORAL_DEMODULATE) ? PT_DENOISE_DEMODULATE : 0u);
+    const f3 Icur = mk(c.x / D.x, c.y / D.y, c.z / D.z);
+    const float l = sv_lum(Icur.x, Icur.y, Icur.z);
+    const float q = l * l;
+    f3 I = Icur;
+    float n = 1.0f, m1 = l, m2 = q;
+    if (A.ph0) {
+        const float W = (float)A.width, H = (float)A.height;
+        const TpMoved mv = tp_move(B.motion, __float_as_uint(a.w), n4, p4);
+        const TpProjection p0 = tp_project(A.cur, p4.x, p4.y, p4.z);
+        const TpProjection p1 = tp_project(A.prev, mv.px, mv.py, mv.pz);
+        const float fx = (float)(int32_t)x + (p1.su - p0.su) * W;
+        const float fy = (float)(int32_t)y + (p1.sv - p0.sv) * H;
+        const bool reproj = p0.z > 0.0f && p1.z > 0.0f && fx > -1.0f && fx < W && fy > -1.0f && fy < H &&
+                            mv.prevId != 0xffffffffu;
+        if (reproj) {
+            const float flx = floorf(fx), fly = floorf(fy);
+            const float ax = fx - flx, ay = fy - fly;
+            const int32_t x0 = (int32_t)flx, y0 = (int32_t)fly;       // -1 .. width - 1, -1 .. height - 1
+            const int32_t Wi = (int32_t)A.width, Hi = (int32_t)A.height;
+            const float m = A.sigmaPlane * n4.w;
+            const float mm = m * m;
+            float sumW = 0.0f, nh = A.maxHistory, sumM1 = 0.0f, sumM2 = 0.0f;
+            f3 sumI = mk(0.0f, 0.0f, 0.0f);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = k & 1, j = k >> 1;
+                const float w = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+                const int32_t qx = x0 + i, qy = y0 + j;
+                const bool inside = qx >= 0 && qx < Wi && qy >= 0 && qy < Hi;
+                const size_t qi = inside ? (size_t)qy * A.width + (uint32_t)qx : pi;
+                const float4 Iq = A.ph0[qi], Nq = A.ph1[qi], Pq = A.ph2[qi], Mq = M.ph3[qi];
+                const float cs = (mv.nx * Nq.x + mv.ny * Nq.y) + mv.nz * Nq.z;
+                const float ex = Pq.x - mv.px, ey = Pq.y - mv.py, ez = Pq.z - mv.pz;
+                const float g = (mv.nx * ex + mv.ny * ey) + mv.nz * ez;
+                const bool skip = !(w > 0.0f) || !inside || Iq.w < 1.0f || !dn_finite(Iq.x) || !dn_finite(Iq.y) ||
+                                  !dn_finite(Iq.z) ||
+                                  ((A.flags & PT_TEMPORAL_SAME_PRIMITIVE) && __float_as_uint(Nq.w) != mv.prevId) ||
+                                  cs < A.normalCosMin || !(g * g <= mm);
+                const float nW = sumW + w;
+                const float nx = sumI.x + w * Iq.x, ny = sumI.y + w * Iq.y, nz = sumI.z + w * Iq.z;
+                const float n1 = sumM1 + w * Mq.x, n2 = sumM2 + w * Mq.y;
+                const float nn = Iq.w < nh ? Iq.w : nh;
+                sumW = skip ? sumW : nW;
+                sumI.x = skip ? sumI.x : nx;
+                sumI.y = skip ? sumI.y : ny;
+                sumI.z = skip ? sumI.z : nz;
+                sumM1 = skip ? sumM1 : n1;
+                sumM2 = skip ? sumM2 : n2;
+                nh = skip ? nh : nn;
+            }
+            if (sumW >= 1.0f / 64.0f) {
+                const f3 Hc = mk(sumI.x / sumW, sumI.y / sumW, sumI.z / sumW);
+                const float Hm1 = sumM1 / sumW, Hm2 = sumM2 / sumW;
+                n = nh + 1.0f;
+                n = n < A.maxHistory ? n : A.maxHistory;
+                float al = 1.0f / n;
+                al = al > A.alphaMin ? al : A.alphaMin;
+                I = mk(Hc.x + al * (Icur.x - Hc.x), Hc.y + al * (Icur.y - Hc.y), Hc.z + al * (Icur.z - Hc.z));
+                m1 = Hm1 + al * (l - Hm1);
+                m2 = Hm2 + al * (q - Hm2);
+            }
+        }
+    }
+    const bool restart = !dn_finite(m1) || !dn_finite(m2);
+    m1 = restart ? l : m1;
+    m2 = restart ? q : m2;
+    A.image[pi] = make_float4(I.x * D.x, I.y * D.y, I.z * D.z, n);
+    A.h0[pi] = make_float4(I.x, I.y, I.z, n);
+    M.h3[pi] = make_float4(m1, m2, sv_clamp0(m2 - m1 * m1), 0.0f);
+}
+
 // ---------------------------------------------------------------------------------------------
 // 2. The variance estimate over the new history.  The temporal tile, one pixel per lane; only a young pixel
 // walks the 7 x 7 window, a row of seven taps of 48 B in flight at a time (the caches serve the overlap).

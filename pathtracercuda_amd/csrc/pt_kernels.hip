@@ -558,6 +558,8 @@ struct pt_context {
     pt_camera tpCam = {};             // its camera
     float tpMs = 0.0f;
     // the history's moments and the variance (pt_svgf.h); no render state
+    float4* motion = nullptr;         // [motionCount][4]: rule 7's table, of the scene set by the last pt_set_scene_moved
+    uint32_t motionCount = 0;
     float4* tmBuf = nullptr;          // [2][pixels] moments planes of tpBuf's two history sets, then [pixels] float: the variance
     hipEvent_t tmEv[3] = {};
     float tmMs[2] = {};               // the step, the estimate
@@ -880,6 +882,7 @@ PT_API void pt_destroy(pt_context* ctx)
     (void)hipFree(ctx->dnBuf);
     (void)hipFree(ctx->tpBuf);
     (void)hipFree(ctx->tmBuf);
+    (void)hipFree(ctx->motion);
     (void)hipFree(ctx->avBuf);
     (void)hipFree(ctx->dsBuf);
     for (auto& e : ctx->dnEv)
@@ -897,6 +900,25 @@ PT_API void pt_destroy(pt_context* ctx)
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
+}
+
+// Rule 7's table as the host arrays give it: refused, or packed into the kernels' four float4 per primitive.
+static const char* motion_table_refusal(uint32_t prim_count, const float* rows, const uint32_t* prev_index)
+{
+    if (!rows || !prev_index) return "motion_rows or prev_index is null";
+    if (prim_count == 0 || prim_count >= (1u << 26)) return "prim_count must be 1 .. 2^26 - 1";
+    return nullptr;
+}
+
+static std::vector<float4> motion_table_pack(uint32_t prim_count, const float* rows, const uint32_t* prev_index)
+{
+    std::vector<float4> e(4 * (size_t)prim_count);
+    for (uint32_t i = 0; i < prim_count; ++i) {
+        const float* r = rows + 12 * (size_t)i;
+        for (int k = 0; k < 3; ++k) e[4 * (size_t)i + k] = make_float4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
+        e[4 * (size_t)i + 3] = make_float4(u2f(prev_index[i]), 0.0f, 0.0f, 0.0f);
+    }
+    return e;
 }
 
 // Host-side validation of the BVH so a malformed scene can never make the kernel read out of
@@ -936,10 +958,11 @@ static int validate_scene(pt_context* ctx, const pt_bvh_node* nodes, uint32_t nn
     return PT_OK;
 }
 
-PT_API int pt_set_scene(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node_count, const pt_hittable* prims,
-                        uint32_t prim_count)
+// pt_set_scene (motion_rows null) and pt_set_scene_moved: the same validation, refusals and uploads; the moved
+// form also checks and uploads rule 7's table and raises scene_moved in place of scene_or_texture_changed.
+static int set_scene_impl(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node_count, const pt_hittable* prims,
+                          uint32_t prim_count, const float* motion_rows, const uint32_t* prev_index)
 {
-    if (!ctx) return PT_ERR_ARG;
     if (node_count == 0 || prim_count == 0 || !nodes || !prims) return fail(ctx, PT_ERR_ARG, "pt_set_scene: empty scene");
     uint32_t maxDepth = 1;
     // nodes reachable from the root: only they are validated, so only they are read below (an
@@ -957,6 +980,19 @@ PT_API int pt_set_scene(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node
                              "(every value must be a finite float)", i, r, c);
                     return fail(ctx, PT_ERR_ARG, buf);
                 }
+    std::vector<float4> table;
+    if (motion_rows) {
+        if (const char* why = motion_table_refusal(prim_count, motion_rows, prev_index))
+            return fail(ctx, PT_ERR_ARG, (std::string("pt_set_scene_moved: ") + why).c_str());
+        for (uint32_t i = 0; i < prim_count; ++i)
+            if (prev_index[i] != 0xffffffffu && prev_index[i] >= ctx->primCount) {
+                char buf[200];
+                snprintf(buf, sizeof(buf), "pt_set_scene_moved: primitive %u: prev_index %u is neither 0xffffffff nor below "
+                         "the %u primitives of the scene it replaces", i, prev_index[i], ctx->primCount);
+                return fail(ctx, PT_ERR_ARG, buf);
+            }
+        table = motion_table_pack(prim_count, motion_rows, prev_index);
+    }
     std::vector<float4> hn(2 * (size_t)node_count), hp(4 * (size_t)prim_count), hm(3 * (size_t)prim_count);
     bool slabFast = true;
     for (uint32_t i = 0; i < node_count; ++i) {
@@ -1047,7 +1083,22 @@ PT_API int pt_set_scene(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node
         ctx->cnodeCount = interior;
     }
     ctx->dfsOrder = dfsOrder;
-    scene_or_texture_changed(ctx->st);
+    if (motion_rows) {
+        // (a failed upload leaves no table: the scene is changed by then, so the history must not survive it)
+        (void)hipFree(ctx->motion);
+        ctx->motion = nullptr;
+        ctx->motionCount = 0;
+        hipError_t e = hipMalloc(&ctx->motion, table.size() * sizeof(float4));
+        if (e == hipSuccess) e = hipMemcpy(ctx->motion, table.data(), table.size() * sizeof(float4), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            scene_or_texture_changed(ctx->st);
+            PT_HIP_CHECK(ctx, e);
+        }
+        ctx->motionCount = prim_count;
+        scene_moved(ctx->st);
+    } else {
+        scene_or_texture_changed(ctx->st);
+    }
     ctx->rootWord = word(0);
     for (int k = 0; k < 3; ++k) {
         ctx->rootBox[2 * k] = nodes[0].aabb_min[k];
@@ -1085,6 +1136,23 @@ PT_API int pt_set_scene(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node
     }
     return PT_OK;
 }
+
+PT_API int pt_set_scene(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node_count, const pt_hittable* prims,
+                        uint32_t prim_count)
+{
+    if (!ctx) return PT_ERR_ARG;
+    return set_scene_impl(ctx, nodes, node_count, prims, prim_count, nullptr, nullptr);
+}
+
+PT_API int pt_set_scene_moved(pt_context* ctx, const pt_bvh_node* nodes, uint32_t node_count, const pt_hittable* prims,
+                              uint32_t prim_count, const float* motion_rows, const uint32_t* prev_index)
+{
+    if (!ctx) return PT_ERR_ARG;
+    if (!motion_rows || !prev_index) return fail(ctx, PT_ERR_ARG, "pt_set_scene_moved: motion_rows or prev_index is null");
+    return set_scene_impl(ctx, nodes, node_count, prims, prim_count, motion_rows, prev_index);
+}
+
+PT_API int pt_holds_motion(const pt_context* ctx) { return ctx && holds_motion(ctx->st) ? 1 : 0; }
 
 PT_API int pt_set_texture(pt_context* ctx, uint32_t handle, const float* rgba, uint32_t width, uint32_t height)
 {

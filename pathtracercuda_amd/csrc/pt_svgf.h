@@ -2,7 +2,8 @@
 // pt_read_temporal_variance, pt_read_temporal_moments_timing, pt_denoise_variance, pt_temporal_moments_image,
 // pt_denoise_variance_image) and of the feedback of the filtered colour into the history
 // (pt_denoise_variance_feedback, pt_read_feedback_timing, pt_read_temporal_history,
-// pt_denoise_variance_feedback_image); the kernels are in pt_dev_svgf.h.  Part of the trace kernel's single
+// pt_denoise_variance_feedback_image), and the moments step across moved objects
+// (pt_temporal_moments_motion_image); the kernels are in pt_dev_svgf.h.  Part of the trace kernel's single
 // translation unit: included by pt_kernels.hip after pt_temporal.h; not a standalone header.
 #pragma once
 
@@ -35,11 +36,12 @@ static bool vdenoise_stage_auto(uint32_t step) { return step <= 2u; }
 
 // The step and the estimate on device buffers of width x height: temporal_run's arguments, with the
 // previous moments plane (read only with prev), the new one and the variance.  ev (optional): 3 events
-// recorded around the two kernels.
+// recorded around the two kernels.  motion (optional): the table of rule 7, and the step is
+// temporal_moments_motion_kernel's.
 static hipError_t moments_run(hipStream_t stream, const pt_temporal_params& p, const pt_variance_params& v, uint32_t width,
                               uint32_t height, const float4* color, const float4* planes, const pt_camera& cur,
                               const float4* prev, const float4* prev3, const pt_camera& prevCam, float4* image, float4* next,
-                              float4* next3, float* var, hipEvent_t* ev)
+                              float4* next3, float* var, hipEvent_t* ev, const MotionTable* motion = nullptr)
 {
     const size_t npix = (size_t)width * height;
     MomentsArgs M = {};
@@ -81,7 +83,12 @@ static hipError_t moments_run(hipStream_t stream, const pt_temporal_params& p, c
     const dim3 grid((width + kDnTileW - 1) / kDnTileW, (height + kDnTileH - 1) / kDnTileH);
     hipError_t e;
     if (ev && (e = hipEventRecord(ev[0], stream)) != hipSuccess) return e;
-    temporal_moments_kernel<<<grid, 256, 0, stream>>>(M);
+    if (motion) {
+        const MomentsMotionArgs B = {M, *motion};
+        temporal_moments_motion_kernel<<<grid, 256, 0, stream>>>(B);
+    } else {
+        temporal_moments_kernel<<<grid, 256, 0, stream>>>(M);
+    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (ev && (e = hipEventRecord(ev[1], stream)) != hipSuccess) return e;
     variance_kernel<<<grid, 256, 0, stream>>>(V);
@@ -229,6 +236,8 @@ PT_API int pt_temporal_moments(pt_context* ctx, uint32_t frames, const pt_tempor
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->rows * ctx->width;
     const bool use = history_held(ctx->st) && history_has_moments(ctx->st) && !reset;
+    const bool moved = holds_motion(ctx->st);                 // asked before the pass begins, as `use`
+    const MotionTable table = {ctx->motion, ctx->motionCount};
     temporal_begins(ctx->st);
     if (!ctx->tpBuf) PT_HIP_CHECK(ctx, hipMalloc(&ctx->tpBuf, 8 * std::max(npix, (size_t)1) * sizeof(float4)));
     if (!ctx->tmBuf) {
@@ -247,7 +256,7 @@ PT_API int pt_temporal_moments(pt_context* ctx, uint32_t frames, const pt_tempor
         PT_HIP_CHECK(ctx, moments_run(ctx->stream, *params, *variance, ctx->width, ctx->height, color, ctx->feat, ctx->featCam,
                                       use ? ctx->tpBuf + (2 + 3 * from) * npix : nullptr, ctx->tmBuf + from * npix, ctx->tpCam,
                                       ctx->tpBuf + npix, ctx->tpBuf + (2 + 3 * to) * npix, ctx->tmBuf + to * npix,
-                                      moments_variance(ctx), ctx->tmEv));
+                                      moments_variance(ctx), ctx->tmEv, moved ? &table : nullptr));
         PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->tmMs[0], ctx->tmEv[0], ctx->tmEv[1]));
         PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->tmMs[1], ctx->tmEv[1], ctx->tmEv[2]));
@@ -363,6 +372,56 @@ PT_API int pt_temporal_moments_image(int device, uint32_t width, uint32_t height
     for (int k = 0; k < 5 && e == hipSuccess; ++k) e = hipMemcpy(out[k], buf + (8 + k) * npix, bytes, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(out_variance, var, npix * sizeof(float), hipMemcpyDeviceToHost);
     (void)hipFree(buf);
+    if (e != hipSuccess) return refuse(PT_ERR_HIP, std::string("HIP error: ") + hipGetErrorString(e));
+    return PT_OK;
+}
+
+PT_API int pt_temporal_moments_motion_image(int device, uint32_t width, uint32_t height, const float* color, const float* plane0,
+                                     const float* plane1, const float* plane2, const pt_camera* cur_cam, const float* hist0,
+                                     const float* hist1, const float* hist2, const float* hist3, const pt_camera* prev_cam,
+                                     const pt_temporal_params* params, const pt_variance_params* variance, float* out_image,
+                                     float* out_hist0, float* out_hist1, float* out_hist2, float* out_hist3, float* out_variance,
+                                            uint32_t prim_count, const float* motion_rows, const uint32_t* prev_index)
+{
+    auto refuse = [](int code, const std::string& msg) {
+        g_freeError = "pt_temporal_moments_motion_image: " + msg;
+        return code;
+    };
+    if (const char* why = temporal_refusal(params)) return refuse(PT_ERR_ARG, why);
+    if (const char* why = variance_refusal(variance)) return refuse(PT_ERR_ARG, why);
+    if (!color || !plane0 || !plane1 || !plane2 || !cur_cam || !out_image || !out_hist0 || !out_hist1 || !out_hist2 ||
+        !out_hist3 || !out_variance)
+        return refuse(PT_ERR_ARG, "an array or cur_cam is null");
+    if (hist0 && (!hist1 || !hist2 || !hist3 || !prev_cam))
+        return refuse(PT_ERR_ARG, "hist0 is given without hist1, hist2, hist3 and prev_cam");
+    if (width == 0 || height == 0 || (uint64_t)width * height >= (1ull << 30) || height > 8u * 0xffffu)
+        return refuse(PT_ERR_ARG, "width x height must be 1 .. 2^30 - 1 pixels, height at most 524280");
+    if (const char* why = motion_table_refusal(prim_count, motion_rows, prev_index)) return refuse(PT_ERR_ARG, why);
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return refuse(PT_ERR_NO_DEVICE, "no GPU visible");
+    if (device < 0 || device >= n) return refuse(PT_ERR_ARG, "device out of range");
+    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
+    float4* buf = nullptr;                  // colour, 3 planes, 4 previous, image, 4 next, the variance
+    const float* in[8] = {color, plane0, plane1, plane2, hist0, hist1, hist2, hist3};
+    float* out[5] = {out_image, out_hist0, out_hist1, out_hist2, out_hist3};
+    const std::vector<float4> entries = motion_table_pack(prim_count, motion_rows, prev_index);
+    float4* table = nullptr;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc(&buf, 13 * bytes + npix * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&table, entries.size() * sizeof(float4));
+    if (e == hipSuccess) e = hipMemcpy(table, entries.data(), entries.size() * sizeof(float4), hipMemcpyHostToDevice);
+    const MotionTable motion = {table, prim_count};
+    for (int k = 0; k < (hist0 ? 8 : 4) && e == hipSuccess; ++k) e = hipMemcpy(buf + k * npix, in[k], bytes, hipMemcpyHostToDevice);
+    float* var = reinterpret_cast<float*>(buf + 13 * npix);
+    if (e == hipSuccess)
+        e = moments_run(nullptr, *params, *variance, width, height, buf, buf + npix, *cur_cam, hist0 ? buf + 4 * npix : nullptr,
+                        buf + 7 * npix, hist0 ? *prev_cam : *cur_cam, buf + 8 * npix, buf + 9 * npix, buf + 12 * npix, var,
+                        nullptr, &motion);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (int k = 0; k < 5 && e == hipSuccess; ++k) e = hipMemcpy(out[k], buf + (8 + k) * npix, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_variance, var, npix * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    (void)hipFree(table);
     if (e != hipSuccess) return refuse(PT_ERR_HIP, std::string("HIP error: ") + hipGetErrorString(e));
     return PT_OK;
 }

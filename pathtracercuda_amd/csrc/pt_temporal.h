@@ -1,5 +1,6 @@
 // Temporal reprojection entry points (pt_temporal, pt_read_temporal, pt_tonemap_temporal,
-// pt_read_temporal_timing, pt_denoise_temporal, pt_temporal_image); the kernel is in pt_dev_temporal.h.
+// pt_read_temporal_timing, pt_denoise_temporal, pt_temporal_image, pt_temporal_motion_image); the kernels are
+// in pt_dev_temporal.h.
 // Part of the trace kernel's single translation unit: included by pt_kernels.hip after pt_denoise.h;
 // not a standalone header.
 #pragma once
@@ -17,10 +18,11 @@ static const char* temporal_refusal(const pt_temporal_params* p)
 }
 
 // One step on device buffers of width x height float4.  planes = 3 planes (pt_render_features' layout);
-// prev = the previous history's 3 planes or null; next = the new history's 3 planes.
+// prev = the previous history's 3 planes or null; next = the new history's 3 planes.  motion (optional): the
+// table of rule 7, and the step is temporal_motion_kernel's.
 static hipError_t temporal_run(hipStream_t stream, const pt_temporal_params& p, uint32_t width, uint32_t height,
                                const float4* color, const float4* planes, const pt_camera& cur, const float4* prev,
-                               const pt_camera& prevCam, float4* image, float4* next)
+                               const pt_camera& prevCam, float4* image, float4* next, const MotionTable* motion = nullptr)
 {
     const size_t npix = (size_t)width * height;
     TemporalArgs A = {};
@@ -45,7 +47,12 @@ static hipError_t temporal_run(hipStream_t stream, const pt_temporal_params& p, 
     A.cur = cur;
     A.prev = prevCam;
     const dim3 grid((width + kDnTileW - 1) / kDnTileW, (height + kDnTileH - 1) / kDnTileH);
-    temporal_kernel<<<grid, 256, 0, stream>>>(A);
+    if (motion) {
+        const TemporalMotionArgs B = {A, *motion};
+        temporal_motion_kernel<<<grid, 256, 0, stream>>>(B);
+    } else {
+        temporal_kernel<<<grid, 256, 0, stream>>>(A);
+    }
     return hipGetLastError();
 }
 
@@ -63,6 +70,8 @@ PT_API int pt_temporal(pt_context* ctx, uint32_t frames, const pt_temporal_param
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t npix = (size_t)ctx->rows * ctx->width;
     const bool use = history_held(ctx->st) && !reset;
+    const bool moved = holds_motion(ctx->st);                 // asked before the pass begins, as `use`
+    const MotionTable table = {ctx->motion, ctx->motionCount};
     temporal_begins(ctx->st);
     if (!ctx->tpBuf) PT_HIP_CHECK(ctx, hipMalloc(&ctx->tpBuf, 8 * std::max(npix, (size_t)1) * sizeof(float4)));
     ctx->tpMs = 0.0f;
@@ -76,7 +85,7 @@ PT_API int pt_temporal(pt_context* ctx, uint32_t frames, const pt_temporal_param
         PT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
         PT_HIP_CHECK(ctx, temporal_run(ctx->stream, *params, ctx->width, ctx->height, color, ctx->feat, ctx->featCam,
                                        use ? ctx->tpBuf + (2 + 3 * from) * npix : nullptr, ctx->tpCam, ctx->tpBuf + npix,
-                                       ctx->tpBuf + (2 + 3 * to) * npix));
+                                       ctx->tpBuf + (2 + 3 * to) * npix, moved ? &table : nullptr));
         PT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
         PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         PT_HIP_CHECK(ctx, hipEventElapsedTime(&ctx->tpMs, ctx->ev0, ctx->ev1));
@@ -166,6 +175,49 @@ PT_API int pt_temporal_image(int device, uint32_t width, uint32_t height, const 
     if (e == hipSuccess) e = hipDeviceSynchronize();
     for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipMemcpy(out[k], buf + (7 + k) * npix, bytes, hipMemcpyDeviceToHost);
     (void)hipFree(buf);
+    if (e != hipSuccess) return refuse(PT_ERR_HIP, std::string("HIP error: ") + hipGetErrorString(e));
+    return PT_OK;
+}
+
+PT_API int pt_temporal_motion_image(int device, uint32_t width, uint32_t height, const float* color, const float* plane0,
+                             const float* plane1, const float* plane2, const pt_camera* cur_cam, const float* hist0,
+                             const float* hist1, const float* hist2, const pt_camera* prev_cam,
+                             const pt_temporal_params* params, float* out_image, float* out_hist0, float* out_hist1,
+                             float* out_hist2, uint32_t prim_count, const float* motion_rows, const uint32_t* prev_index)
+{
+    auto refuse = [](int code, const std::string& msg) {
+        g_freeError = "pt_temporal_motion_image: " + msg;
+        return code;
+    };
+    if (const char* why = temporal_refusal(params)) return refuse(PT_ERR_ARG, why);
+    if (!color || !plane0 || !plane1 || !plane2 || !cur_cam || !out_image || !out_hist0 || !out_hist1 || !out_hist2)
+        return refuse(PT_ERR_ARG, "an array or cur_cam is null");
+    if (hist0 && (!hist1 || !hist2 || !prev_cam)) return refuse(PT_ERR_ARG, "hist0 is given without hist1, hist2 and prev_cam");
+    if (width == 0 || height == 0 || (uint64_t)width * height >= (1ull << 30) || height > 8u * 0xffffu)
+        return refuse(PT_ERR_ARG, "width x height must be 1 .. 2^30 - 1 pixels, height at most 524280");
+    if (const char* why = motion_table_refusal(prim_count, motion_rows, prev_index)) return refuse(PT_ERR_ARG, why);
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return refuse(PT_ERR_NO_DEVICE, "no GPU visible");
+    if (device < 0 || device >= n) return refuse(PT_ERR_ARG, "device out of range");
+    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
+    float4* buf = nullptr;                  // colour, 3 planes, 3 previous, image, 3 next
+    const float* in[7] = {color, plane0, plane1, plane2, hist0, hist1, hist2};
+    float* out[4] = {out_image, out_hist0, out_hist1, out_hist2};
+    const std::vector<float4> entries = motion_table_pack(prim_count, motion_rows, prev_index);
+    float4* table = nullptr;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc(&buf, 11 * bytes);
+    if (e == hipSuccess) e = hipMalloc(&table, entries.size() * sizeof(float4));
+    if (e == hipSuccess) e = hipMemcpy(table, entries.data(), entries.size() * sizeof(float4), hipMemcpyHostToDevice);
+    const MotionTable motion = {table, prim_count};
+    for (int k = 0; k < (hist0 ? 7 : 4) && e == hipSuccess; ++k) e = hipMemcpy(buf + k * npix, in[k], bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = temporal_run(nullptr, *params, width, height, buf, buf + npix, *cur_cam, hist0 ? buf + 4 * npix : nullptr,
+                         hist0 ? *prev_cam : *cur_cam, buf + 7 * npix, buf + 8 * npix, &motion);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipMemcpy(out[k], buf + (7 + k) * npix, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    (void)hipFree(table);
     if (e != hipSuccess) return refuse(PT_ERR_HIP, std::string("HIP error: ") + hipGetErrorString(e));
     return PT_OK;
 }

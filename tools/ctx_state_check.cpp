@@ -44,26 +44,26 @@ static void (*const kEventFns[])(CtxState&) = {
     scene_or_texture_changed, rng_written, schedule_changed, order_dropped, order_replaced, order_biased,
     accum_written, stash_made, adaptive_begins, adaptive_done, features_begin, features_done, denoise_begins, denoise_done,
     temporal_begins, temporal_done, moments_done, adaptive_variance_begins, adaptive_variance_done, despike_begins,
-    despike_done};
+    despike_done, scene_moved};
 static const char* const kEventNames[] = {
     "scene_or_texture_changed", "rng_written", "schedule_changed", "order_dropped", "order_replaced",
     "order_biased", "accum_written", "stash_made", "adaptive_begins", "adaptive_done", "features_begin", "features_done",
     "denoise_begins", "denoise_done", "temporal_begins", "temporal_done", "moments_done", "adaptive_variance_begins",
-    "adaptive_variance_done", "despike_begins", "despike_done"};
+    "adaptive_variance_done", "despike_begins", "despike_done", "scene_moved"};
 constexpr int kEvents = sizeof(kEventFns) / sizeof(kEventFns[0]);
 // the tool's own list of the events after which a sample is no longer what the last render's was
 static bool moves_epoch(void (*event)(CtxState&))
 {
-    return event == scene_or_texture_changed || event == rng_written || event == adaptive_begins;
+    return event == scene_or_texture_changed || event == rng_written || event == adaptive_begins || event == scene_moved;
 }
 static_assert(kEvents == sizeof(kEventNames) / sizeof(kEventNames[0]), "one name per event");
 
 static bool (*const kPredicates[])(const CtxState&) = {counts_describe_buffer, moments_continue, planes_current, holds_denoised,
                                                        holds_temporal, history_held, temporal_of_planes, history_has_moments,
-                                                       variance_of_counts, holds_despiked};
+                                                       variance_of_counts, holds_despiked, holds_motion};
 static const char* const kPredicateNames[] = {"counts_describe_buffer", "moments_continue", "planes_current", "holds_denoised",
                                               "holds_temporal", "history_held", "temporal_of_planes", "history_has_moments",
-                                              "variance_of_counts", "holds_despiked"};
+                                              "variance_of_counts", "holds_despiked", "holds_motion"};
 constexpr int kPredicateCount = sizeof(kPredicates) / sizeof(kPredicates[0]);
 static_assert(kPredicateCount == sizeof(kPredicateNames) / sizeof(kPredicateNames[0]), "one name per predicate");
 
@@ -94,6 +94,7 @@ struct Fuzz {
         const bool hist = s.histValid, mom = s.momValid;
         const bool av = s.avValid, counts = s.adCountsValid;
         const bool ds = s.dsValid, feat = s.featValid;
+        const bool motion = s.motionValid;
         const uint32_t e = next() % (kEvents + 6);       // (a render as likely as four other events)
         if (e < (uint32_t)kEvents) {
             kEventFns[e](s);
@@ -108,6 +109,7 @@ struct Fuzz {
             check(s.histValid == (hist && held == handle));
             check(s.momValid == (mom && held == handle));
             check(s.dsValid == (ds && held == handle));          // another sky: the image's colours are of the old one
+            check(s.motionValid == (motion && held == handle));  // the table goes with the history
         } else {
             const unsigned long long cam = next() % 3;
             const RenderStart r = render_begins(s, camera_of(cam));
@@ -123,10 +125,12 @@ struct Fuzz {
         check(!s.momValid || s.histValid);
         check(!s.avValid || s.adCountsValid);
         check(!s.dsValid || s.featValid);                // the despiked image is of the planes the context holds
+        check(!s.motionValid || s.histValid);            // the table maps to the scene of a history that is held
         // the tool's own list of what ends a history and what does not
         if (e < (uint32_t)kEvents) {
             void (*const f)(CtxState&) = kEventFns[e];
-            const bool ends = f == scene_or_texture_changed || f == temporal_begins;
+            // (a move ends the history only when it is the second one since a temporal pass)
+            const bool ends = f == scene_or_texture_changed || f == temporal_begins || (f == scene_moved && motion);
             if (f != temporal_done) check(s.histValid == (hist && !ends));
             if (f == features_begin) check(!s.tpOfPlanes);
             // the moments end with the history (a plain temporal step begins as every step and sets them no more);
@@ -140,10 +144,17 @@ struct Fuzz {
             // the tool's own list of what ends the despiked image: its own beginning, what writes the accumulation (a
             // render is checked above), a features call that begins, a scene or texture change (another sky is checked
             // above); only a finished pt_despike over current planes sets it
-            const bool endsDs = f == despike_begins || f == adaptive_begins || f == features_begin || f == scene_or_texture_changed;
+            const bool endsDs = f == despike_begins || f == adaptive_begins || f == features_begin ||
+                                f == scene_or_texture_changed || f == scene_moved;
             check(s.dsValid == (f == despike_done ? feat : (ds && !endsDs)));
+            // the tool's own list of what ends the motion table: a temporal pass that begins, a scene or texture change
+            // (another sky is checked above), a second move; only a first move over a held history sets it
+            const bool endsMotion = f == temporal_begins || f == scene_or_texture_changed;
+            check(s.motionValid == (f == scene_moved ? (hist && !motion) : (motion && !endsMotion)));
+            if (f == scene_moved) check(!s.featValid && s.stateEpoch == stateEpoch + 1 && s.order.stale);
         } else if (e != (uint32_t)kEvents + 1) {
             check(s.histValid == hist && s.momValid == mom);     // a sort of the order, a render
+            check(s.motionValid == motion);
             if (e == (uint32_t)kEvents) check(s.avValid == av && s.dsValid == ds);
         } else {
             check(s.avValid == av);                              // a sky ends no variance of the counts
@@ -158,12 +169,13 @@ static void print_state(const CtxState& s, const std::string& extra)
     printf("{\"order\": {\"valid\": %d, \"stale\": %d, \"samples\": %llu, \"strip\": %u}, \"stateEpoch\": %llu, "
            "\"lastState\": %llu, \"launched\": %d, \"lastCam\": %d, \"aheadValid\": %d, \"aheadMisses\": %u, \"adMomValid\": %d, "
            "\"adCountsValid\": %d, \"featValid\": %d, \"dnValid\": %d, \"tpValid\": %d, \"histValid\": %d, "
-           "\"tpOfPlanes\": %d, \"momValid\": %d, \"avValid\": %d, \"dsValid\": %d, \"epoch\": %llu%s}\n",
+           "\"tpOfPlanes\": %d, \"momValid\": %d, \"avValid\": %d, \"dsValid\": %d, \"motionValid\": %d, "
+           "\"epoch\": %llu%s}\n",
            (int)s.order.valid, (int)s.order.stale, (unsigned long long)s.order.samples, s.order.strip,
            (unsigned long long)s.stateEpoch, (unsigned long long)s.lastState, (int)s.launched, (int)s.lastCam.origin[0],
            (int)s.aheadValid, s.aheadMisses, (int)s.adMomValid, (int)s.adCountsValid, (int)s.featValid, (int)s.dnValid,
            (int)s.tpValid, (int)s.histValid, (int)s.tpOfPlanes, (int)s.momValid, (int)s.avValid, (int)s.dsValid,
-           (unsigned long long)s.epoch, extra.c_str());
+           (int)s.motionValid, (unsigned long long)s.epoch, extra.c_str());
     fflush(stdout);
 }
 
