@@ -7,6 +7,9 @@
 #                                         tests/test_gpu_dev_functions.py (GPU)
 #   pathtracercuda_amd/lib/ssg_stages     the guess, lane and fold code of speculative sample groups stage by
 #                                         stage over files, for tests/test_gpu_ssg_stages.py (GPU)
+#   pathtracercuda_amd/lib/ray_forms      the slab test, the child-pair test and the object-space transform against
+#                                         the packed-FP32 forms they replaced, for tests/test_gpu_ray_forms.py (GPU)
+#   pathtracercuda_amd/lib/pk_issue_probe issue cost of packed against plain FP32 instructions (GPU; `make pkprobe`)
 #   pathtracercuda_amd/lib/host_sanitize_check  ASan/UBSan mutation check of the host parsers (CPU)
 #   pathtracercuda_amd/lib/leaf_forms_check  exact vs fast form of the cube leaf test (CPU; `make leafcheck` runs it)
 #   pathtracercuda_amd/lib/launch_plan_check  the launch policy and the build table on the host, for tests/test_launch_plan.py (CPU)
@@ -27,7 +30,8 @@ HOST_SRCS := $(SRC)/host/math_camera.cpp $(SRC)/host/hittable.cpp $(SRC)/host/bv
              $(SRC)/host/renderer.cpp $(SRC)/host/host_capi.cpp
 HOST_HDRS := include/pathtracer_amd.hpp include/pt_host.h include/pt_hip.h $(SRC)/host/host_internal.h $(SRC)/host/json_min.h
 
-# -fno-slp-vectorize: the kernel's packed FP32 pairs are written out (ext_vector_type); the SLP
+# -fno-slp-vectorize: the kernel uses no packed FP32 (plain instructions measured faster, DESIGN.md
+# §4.1; tools/ray_forms.hip keeps the packed forms as a reference); the SLP
 # vectorizer's own pairings bound two scalars of the GGX visibility term into one register tuple
 # that the allocator then spilled around a range guard in every GGX shading.  Off: scratch 40 -> 12
 # B/lane (no spill inside the loop), +4.6 % on C3 same-box (profiles/r03_slp_ab.json).
@@ -38,7 +42,7 @@ HIPFLAGS ?= $(HIPCODEGEN) -fPIC -fvisibility=hidden -Iinclude -Wall -Wno-unused-
 CXXFLAGS ?= -O2 -std=c++17 -ffp-contract=off -fno-fast-math -fPIC -Iinclude -I$(SRC)/host -Wall -Wextra \
             -Wno-unused-parameter -Wno-missing-field-initializers
 
-all: $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer $(LIB)/fp_exhaustive $(LIB)/dev_functions $(LIB)/ssg_stages $(LIB)/host_sanitize_check $(LIB)/leaf_forms_check $(LIB)/launch_plan_check $(LIB)/ctx_state_check oracle
+all: $(LIB)/libpt_hip.so $(LIB)/libpt_host.so $(LIB)/pathtracer $(LIB)/fp_exhaustive $(LIB)/dev_functions $(LIB)/ssg_stages $(LIB)/ray_forms $(LIB)/pk_issue_probe $(LIB)/host_sanitize_check $(LIB)/leaf_forms_check $(LIB)/launch_plan_check $(LIB)/ctx_state_check oracle
 
 $(LIB):
 	mkdir -p $(LIB)
@@ -62,6 +66,17 @@ $(LIB)/dev_functions: tools/dev_functions.hip $(SRC)/pt_math.h $(SRC)/pt_dev_tex
 # The sample-group stages on a toy stream (tools/ssg_stages.hip): the kernel's own headers, in its order.
 $(LIB)/ssg_stages: tools/ssg_stages.hip $(wildcard $(SRC)/*.h) include/pt_hip.h | $(LIB)
 	$(HIPCC) $(HIPCODEGEN) -Wall -o $@ tools/ssg_stages.hip
+
+# The slab test, cb_pair and to_local against their packed-FP32 forms (tools/ray_forms.hip): the kernel's own
+# headers, in its order.
+$(LIB)/ray_forms: tools/ray_forms.hip $(wildcard $(SRC)/*.h) include/pt_hip.h | $(LIB)
+	$(HIPCC) $(HIPCODEGEN) -Wall -o $@ tools/ray_forms.hip
+
+# Cycles per packed and per plain FP32 instruction at 1, 2 and 6 waves per SIMD (tools/pk_issue_probe.hip).
+$(LIB)/pk_issue_probe: tools/pk_issue_probe.hip | $(LIB)
+	$(HIPCC) $(HIPCODEGEN) -Wall -o $@ tools/pk_issue_probe.hip
+pkprobe: $(LIB)/pk_issue_probe
+	$(LIB)/pk_issue_probe
 
 oracle:
 	$(MAKE) -C oracle REF=$(REF)
@@ -101,7 +116,7 @@ clean:
 clean-ref:
 	$(MAKE) -C oracle clean-ref
 
-.PHONY: all oracle clean clean-ref sanitize leafcheck
+.PHONY: all oracle clean clean-ref sanitize leafcheck pkprobe
 
 # `make -s print-HIPFLAGS`: the flags snapshot builds (tools/snap_rev.sh) reuse
 print-%:

@@ -116,30 +116,23 @@ enum : uint32_t { SPHERE = 0, CYLINDER = 1, DISK = 2, CONE = 3, PARABOLOID = 4, 
 
 struct LocalRay { f3 o, d; };
 
-typedef float f2v __attribute__((ext_vector_type(2)));   // lowers to v_pk_{add,mul}_f32 on gfx950
-
-PT_DEV f2v f2(float a, float b) { return (f2v){a, b}; }
-
 // Hittable.inl:91-98: world -> object space with the 3x4 inverse rows (origin gets +w).  Device
 // layout of the rows (pt_set_scene): P0 = (r0.x, r1.x, r0.y, r1.y), P1 = (r0.z, r1.z, r0.w, r1.w),
-// P2 = row 2, so the x and y components are evaluated pairwise with packed FP32 ops -- the same
-// products and sums in the same order as the reference's dot products, two lanes of a
-// v_pk_mul/v_pk_add at a time (exactly rounded per element; no FMA contraction).
+// P2 = row 2.  Every component is the reference's dot product: the same products and sums in the same
+// order, one plain FP32 instruction each (exactly rounded; no FMA contraction).  The paired order of
+// rows 0 and 1 dates from a form that evaluated x and y two at a time with v_pk_mul_f32 / v_pk_add_f32.
+// In the kernel that form measured slower (C3 -1.6 % for this site alone, profiles/r08_scalar_forms.json):
+// a packed instruction saves little issue time over the two plain ones it stands for (DESIGN.md §4.3,
+// tools/pk_issue_probe.hip), and its operands are register pairs that have to be put together first.
+// tools/ray_forms.hip holds the packed form as the reference this one is compared with word for word.
 PT_DEV LocalRay to_local(const float4& P0, const float4& P1, const float4& r2, f3 o, f3 d)
 {
     LocalRay l;
-    f2v oxy = f2(P0.x, P0.y) * f2(o.x, o.x);
-    oxy = oxy + f2(P0.z, P0.w) * f2(o.y, o.y);
-    oxy = oxy + f2(P1.x, P1.y) * f2(o.z, o.z);
-    oxy = oxy + f2(P1.z, P1.w);
-    f2v dxy = f2(P0.x, P0.y) * f2(d.x, d.x);
-    dxy = dxy + f2(P0.z, P0.w) * f2(d.y, d.y);
-    dxy = dxy + f2(P1.x, P1.y) * f2(d.z, d.z);
-    l.o.x = oxy.x;
-    l.o.y = oxy.y;
+    l.o.x = ((P0.x * o.x + P0.z * o.y) + P1.x * o.z) + P1.z;
+    l.o.y = ((P0.y * o.x + P0.w * o.y) + P1.y * o.z) + P1.w;
     l.o.z = (o.x * r2.x + o.y * r2.y + o.z * r2.z) + r2.w;
-    l.d.x = dxy.x;
-    l.d.y = dxy.y;
+    l.d.x = (P0.x * d.x + P0.z * d.y) + P1.x * d.z;
+    l.d.y = (P0.y * d.x + P0.w * d.y) + P1.y * d.z;
     l.d.z = d.x * r2.x + d.y * r2.y + d.z * r2.z;
     return l;
 }
@@ -368,20 +361,20 @@ PT_DEV bool slab_fast_ray(bool slabFast, f3 o, float ix, float iy, float iz)
 // Fast form, exact when the ray's origin and 1/d are finite on all axes, the box is not inverted (checked per ray
 // and per scene) and t_max is not NaN (v_min3 would drop it; the walk leaves the fast form when a hit
 // distance is NaN): then no product is NaN, the swap on a negative 1/d is min/max of the two slab
-// distances, and the running max/min over the axes is order-independent, so v_max3/v_min3 and
-// packed subtract/multiply give the reference's values.
-PT_DEV NodeHit node_test_fast(const float4* __restrict__ nodes, uint32_t cur, f2v ox2, f2v oy2, f2v oz2, f2v ix2,
-                              f2v iy2, f2v iz2, float tMin, float tMax)
+// distances, and the running max/min over the axes is order-independent, so v_max3/v_min3 over the
+// six subtract/multiply results give the reference's values.
+PT_DEV NodeHit node_test_fast(const float4* __restrict__ nodes, uint32_t cur, f3 o, float ix, float iy, float iz,
+                              float tMin, float tMax)
 {
     const float4 A = nodes[2 * cur];
     const float4 Bq = nodes[2 * cur + 1];
-    const f2v tx = (f2(A.x, A.y) - ox2) * ix2;
-    const f2v ty = (f2(A.z, A.w) - oy2) * iy2;
-    const f2v tz = (f2(Bq.x, Bq.y) - oz2) * iz2;
-    const float lo = __builtin_fmaxf(__builtin_fmaxf(tMin, __builtin_fminf(tx.x, tx.y)),
-                                     __builtin_fmaxf(__builtin_fminf(ty.x, ty.y), __builtin_fminf(tz.x, tz.y)));
-    const float hi = __builtin_fminf(__builtin_fminf(tMax, __builtin_fmaxf(tx.x, tx.y)),
-                                     __builtin_fminf(__builtin_fmaxf(ty.x, ty.y), __builtin_fmaxf(tz.x, tz.y)));
+    const float tx0 = (A.x - o.x) * ix, tx1 = (A.y - o.x) * ix;
+    const float ty0 = (A.z - o.y) * iy, ty1 = (A.w - o.y) * iy;
+    const float tz0 = (Bq.x - o.z) * iz, tz1 = (Bq.y - o.z) * iz;
+    const float lo = __builtin_fmaxf(__builtin_fmaxf(tMin, __builtin_fminf(tx0, tx1)),
+                                     __builtin_fmaxf(__builtin_fminf(ty0, ty1), __builtin_fminf(tz0, tz1)));
+    const float hi = __builtin_fminf(__builtin_fminf(tMax, __builtin_fmaxf(tx0, tx1)),
+                                     __builtin_fminf(__builtin_fmaxf(ty0, ty1), __builtin_fmaxf(tz0, tz1)));
     return NodeHit{hi > lo, __float_as_uint(Bq.z), __float_as_uint(Bq.w)};
 }
 
@@ -405,10 +398,8 @@ PT_DEV uint32_t traverse(const float4* __restrict__ nodes, const float4* __restr
     // trace.cu:31-36: dirIsNeg from 1/(d != 0 ? d : 1e-7) < 0, i.e. d < 0
     const uint32_t negMask = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
     bool fast = slab_fast_ray(slabFast, o, ix, iy, iz);
-    const f2v ox2 = f2(o.x, o.x), oy2 = f2(o.y, o.y), oz2 = f2(o.z, o.z);
-    const f2v ix2 = f2(ix, ix), iy2 = f2(iy, iy), iz2 = f2(iz, iz);
     auto test = [&](uint32_t node) {
-        return fast ? node_test_fast(nodes, node, ox2, oy2, oz2, ix2, iy2, iz2, tMin, tMax)
+        return fast ? node_test_fast(nodes, node, o, ix, iy, iz, tMin, tMax)
                     : node_test(nodes, node, o, ix, iy, iz, tMin, tMax);
     };
     uint32_t sp = 0, cur = 0, elem = 0xffffffffu;

@@ -24,31 +24,34 @@
 // lane are unchanged; a visit costs one dependent fetch instead of two, and leaves cost none.
 // ---------------------------------------------------------------------------------------------
 struct SlabRay {
-    f2v ox2, oy2, oz2, ix2, iy2, iz2;
     f3 o;
     float ix, iy, iz;
     bool fast;
 };
 
-// lo and X of one box (see above); the fast form under the same conditions as node_test_fast.
+// lo and X of one box (see above), given as its (low, high) pair per axis; the fast form under the same
+// conditions as node_test_fast: six plain subtract/multiply pairs.  (They replaced three packed pairs on
+// duplicated copies (o.x, o.x), (ix, ix), ... of the ray -- twelve VGPRs for six values, under the six-wave
+// cap of 80: C3 -5.3 % for this site alone, DESIGN.md §4.1, profiles/r08_scalar_forms.json;
+// tools/ray_forms.hip compares the two forms word for word.)
 template <bool ALLFAST = false>
-PT_DEV float slab_lo_x(const SlabRay& R, f2v bx, f2v by, f2v bz, float tMin, float& X)
+PT_DEV float slab_lo_x(const SlabRay& R, float x0, float x1, float y0, float y1, float z0, float z1, float tMin, float& X)
 {
     if (ALLFAST || R.fast) {
-        const f2v tx = (bx - R.ox2) * R.ix2;
-        const f2v ty = (by - R.oy2) * R.iy2;
-        const f2v tz = (bz - R.oz2) * R.iz2;
-        X = __builtin_fminf(__builtin_fmaxf(tx.x, tx.y), __builtin_fminf(__builtin_fmaxf(ty.x, ty.y), __builtin_fmaxf(tz.x, tz.y)));
-        return __builtin_fmaxf(__builtin_fmaxf(tMin, __builtin_fminf(tx.x, tx.y)),
-                               __builtin_fmaxf(__builtin_fminf(ty.x, ty.y), __builtin_fminf(tz.x, tz.y)));
+        const float tx0 = (x0 - R.o.x) * R.ix, tx1 = (x1 - R.o.x) * R.ix;
+        const float ty0 = (y0 - R.o.y) * R.iy, ty1 = (y1 - R.o.y) * R.iy;
+        const float tz0 = (z0 - R.o.z) * R.iz, tz1 = (z1 - R.o.z) * R.iz;
+        X = __builtin_fminf(__builtin_fmaxf(tx0, tx1), __builtin_fminf(__builtin_fmaxf(ty0, ty1), __builtin_fmaxf(tz0, tz1)));
+        return __builtin_fmaxf(__builtin_fmaxf(tMin, __builtin_fminf(tx0, tx1)),
+                               __builtin_fmaxf(__builtin_fminf(ty0, ty1), __builtin_fminf(tz0, tz1)));
     }
     float lo = tMin, hi = __builtin_inff();
     const float inv[3] = {R.ix, R.iy, R.iz};
     const float org[3] = {R.o.x, R.o.y, R.o.z};
-    const f2v b[3] = {bx, by, bz};
+    const float b0[3] = {x0, y0, z0}, b1[3] = {x1, y1, z1};
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        float t0 = (b[k].x - org[k]) * inv[k], t1 = (b[k].y - org[k]) * inv[k];
+        float t0 = (b0[k] - org[k]) * inv[k], t1 = (b1[k] - org[k]) * inv[k];
         if (inv[k] < 0.0f) { const float tmp = t0; t0 = t1; t1 = tmp; }
         lo = t0 > lo ? t0 : lo;
         hi = t1 < hi ? t1 : hi;
@@ -79,9 +82,6 @@ PT_DEV void slab_restore(SlabRay& R, f3 d, bool slabFast)
     R.iy = 1.0f / d.y;
     R.iz = 1.0f / d.z;
     R.fast = slab_fast_ray(slabFast, R.o, R.ix, R.iy, R.iz);
-    R.ix2 = f2(R.ix, R.ix);
-    R.iy2 = f2(R.iy, R.iy);
-    R.iz2 = f2(R.iz, R.iz);
 }
 
 // Both children of interior record `cur`, in the reference's visit order (trace.cu:66-77: near =
@@ -107,8 +107,8 @@ PT_DEV ChildPair cb_pair(const float4& Q0, const float4& Q1, const float4& Q2, c
                          uint32_t negMask, float tMin, float tMax)
 {
     float XL, XR;
-    const float loL = slab_lo_x<ALLFAST>(R, f2(Q0.x, Q0.y), f2(Q0.z, Q0.w), f2(Q1.x, Q1.y), tMin, XL);
-    const float loR = slab_lo_x<ALLFAST>(R, f2(Q2.x, Q2.y), f2(Q2.z, Q2.w), f2(Q1.z, Q1.w), tMin, XR);
+    const float loL = slab_lo_x<ALLFAST>(R, Q0.x, Q0.y, Q0.z, Q0.w, Q1.x, Q1.y, tMin, XL);
+    const float loR = slab_lo_x<ALLFAST>(R, Q2.x, Q2.y, Q2.z, Q2.w, Q1.z, Q1.w, tMin, XR);
     const bool isNeg = (negMask & __float_as_uint(Q3.z)) != 0u;
     const uint32_t wL = __float_as_uint(Q3.x), wR = __float_as_uint(Q3.y);
     const bool hL = XL > loL && !(tMax <= loL);   // (a NaN t_max passes: slab_pass_all)
@@ -149,8 +149,8 @@ PT_DEV void repair_pending(const float4* __restrict__ cnodes, uint2* stack, cons
         const bool inR = leafOff >= __float_as_uint(Q3.w);
         const bool isNeg = (negMask & __float_as_uint(Q3.z)) != 0u;   // near child = second when negative
         float X;                                                     // the other child's box (Q0..Q2 layout)
-        const float lo = slab_lo_x(R, inR ? f2(Q0.x, Q0.y) : f2(Q2.x, Q2.y), inR ? f2(Q0.z, Q0.w) : f2(Q2.z, Q2.w),
-                                   inR ? f2(Q1.x, Q1.y) : f2(Q1.z, Q1.w), tMin, X);
+        const float4 Qo = inR ? Q0 : Q2;
+        const float lo = slab_lo_x(R, Qo.x, Qo.y, Qo.z, Qo.w, inR ? Q1.x : Q1.z, inR ? Q1.y : Q1.w, tMin, X);
         if (inR == isNeg && X > lo) {                                // the path took the near child
             stack[64u * sp] = make_uint2(__float_as_uint(inR ? Q3.x : Q3.y), __float_as_uint(lo));
             ++sp;
@@ -172,12 +172,6 @@ PT_DEV uint32_t traverse_cb(const float4* __restrict__ cnodes, const float4* __r
     R.iy = rcp_rn(d.y);
     R.iz = rcp_rn(d.z);
     R.fast = slab_fast_ray(P.slabFast != 0, R.o, R.ix, R.iy, R.iz);
-    R.ox2 = f2(o.x, o.x);
-    R.oy2 = f2(o.y, o.y);
-    R.oz2 = f2(o.z, o.z);
-    R.ix2 = f2(R.ix, R.ix);
-    R.iy2 = f2(R.iy, R.iy);
-    R.iz2 = f2(R.iz, R.iz);
     const uint32_t negMask = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
     uint32_t sp = 0, elem = 0xffffffffu, cur = P.rootWord;
     // pops the next pending far child that still passes its box test under the current t_max
@@ -190,8 +184,8 @@ PT_DEV uint32_t traverse_cb(const float4* __restrict__ cnodes, const float4* __r
     };
     if (STATS) { cnt.node_tests++; wave_tick(cnt.w_node); }
     float X;
-    const float lo0 = slab_lo_x(R, f2(P.rootBox[0], P.rootBox[1]), f2(P.rootBox[2], P.rootBox[3]),
-                                f2(P.rootBox[4], P.rootBox[5]), tMin, X);
+    const float lo0 = slab_lo_x(R, P.rootBox[0], P.rootBox[1], P.rootBox[2], P.rootBox[3], P.rootBox[4], P.rootBox[5],
+                                tMin, X);
     bool done = !(X > lo0 && tMax > lo0);
     uint64_t tPhase = STATS ? __builtin_amdgcn_s_memtime() : 0;
     while (!done) {
@@ -335,12 +329,6 @@ PT_DEV bool traverse_cb_phase(const float4* __restrict__ cnodes, const float4* _
             R.fast = ok ? R.fast : slab_fast_ray(P.slabFast != 0, o, gx, gy, gz);
         }
     }
-    R.ox2 = f2(o.x, o.x);
-    R.oy2 = f2(o.y, o.y);
-    R.oz2 = f2(o.z, o.z);
-    R.ix2 = f2(R.ix, R.ix);
-    R.iy2 = f2(R.iy, R.iy);
-    R.iz2 = f2(R.iz, R.iz);
     const uint32_t negMask = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
     const uint32_t nAct = (uint32_t)__popcll(__ballot(1));
     if (fresh) {
@@ -349,8 +337,8 @@ PT_DEV bool traverse_cb_phase(const float4* __restrict__ cnodes, const float4* _
         ts.elem = 0xffffffffu;
         if (STATS) { cnt.node_tests++; wave_tick(cnt.w_node); }
         float X;
-        const float lo0 = slab_lo_x(R, f2(P.rootBox[0], P.rootBox[1]), f2(P.rootBox[2], P.rootBox[3]),
-                                    f2(P.rootBox[4], P.rootBox[5]), tMin, X);
+        const float lo0 = slab_lo_x(R, P.rootBox[0], P.rootBox[1], P.rootBox[2], P.rootBox[3], P.rootBox[4],
+                                    P.rootBox[5], tMin, X);
         ts.cur = (X > lo0 && ts.tMax > lo0) ? P.rootWord : kWalkDone;
     }
     uint32_t sp = ts.sp, cur = ts.cur, elem = ts.elem;
