@@ -268,6 +268,25 @@ public:
     void despike() { despike(DespikeOptions()); }
     uint32_t despikeCount();
     bool despiked() const;                           // a despiked image made through this class is still held
+    // Guided upsampling (pt_upsample, rule 8 of pt_hip.h): this Pathtracer reconstructs its frame from the image of
+    // `lo`, a Pathtracer of the same scene and camera at a lower resolution on the same device.  Both need
+    // renderFeatures(camera); this one needs no render.  source: one of PT_UPSAMPLE_*, or kUpsampleAuto = what lo's
+    // image calls return (its denoised image, else its despiked image, else its accumulation over its frames or
+    // per-pixel counts).  While the upsampled image is held (until the next render, scene, texture or sky change or
+    // filter call on this Pathtracer) getHDRImageData / getImageData return it.  Nothing of `lo` changes.
+    // upsampleCounts: the pixels that needed the wider ring, and those that took the nearest low pixel.  Single device only.
+    static constexpr uint32_t kUpsampleAuto = 0xffffffffu;
+    struct UpsampleOptions {
+        uint32_t source = kUpsampleAuto;
+        float sigmaPlane = PT_UPSAMPLE_DEFAULT_SIGMA_PLANE;
+        uint32_t normalPowerLog2 = PT_UPSAMPLE_DEFAULT_NORMAL_POWER_LOG2;
+        uint32_t flags = PT_UPSAMPLE_DEFAULT_FLAGS;
+        uint32_t staging = 0;
+    };
+    void upsample(Pathtracer& lo, const UpsampleOptions& options);
+    void upsample(Pathtracer& lo) { upsample(lo, UpsampleOptions()); }
+    void upsampleCounts(uint32_t counts[2]);
+    bool upsampled() const;                          // an upsampled image made through this class is still held
     // Temporal reprojection (pt_temporal, pt_hip.h): per frame render(camera, spp, true), renderFeatures(camera),
     // temporal().  The result of the previous temporal() is reprojected into this frame's camera, rejected
     // where it is no longer the same surface, and this frame blended in.  Returns whether a previous history
@@ -368,6 +387,7 @@ private:
     bool m_adaptive = false;
     bool m_denoised = false;
     bool m_despiked = false;           // this class made a despiked image and nothing through it has ended it
+    bool m_upsampled = false;          // this class made an upsampled image and nothing through it has ended it
     std::vector<float> m_featureBuffer;
     std::vector<float> m_temporalBuffer;
     std::vector<float> m_varianceBuffer;
@@ -407,6 +427,7 @@ struct Params {
     float m_adaptive = -1.0f;        // CLI -adaptive <tolerance>: >= 0 renders adaptively, m_spp is the budget
     unsigned int m_minSpp = 0;       // CLI -minspp: samples every pixel gets (0 = two calls)
     bool m_despike = false;          // CLI -despike: the firefly clamp at its defaults before the image is written
+    unsigned int m_upsample = 0;     // CLI -upsample K: trace at ceil(w / K) x ceil(h / K) and reconstruct the frame (0 = off)
     unsigned int m_denoise = 0;      // CLI -denoise [N]: a-trous iterations applied before the image is written (0 = off)
     bool m_denoiseAdaptive = false;  // CLI -denoise_guide adaptive: the filter follows the adaptive render's own variance
 };

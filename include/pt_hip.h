@@ -889,6 +889,113 @@ PT_API int pt_despike_image(int device, uint32_t width, uint32_t height, const f
                             const float *plane1, const float *plane2, const pt_despike_params *params, float *out,
                             uint32_t *out_count);
 
+/* ---- Guided upsampling of a low-resolution image to the full frame -----------------------------------
+ * Tracing costs per pixel; the first-hit planes are one ray per pixel.  Rule 8 takes a colour image and its planes
+ * at w x h (what was traced, and filtered if wanted) and the planes at W x H (what is shown), and gives every high
+ * pixel the demodulated colour of the low pixels around it that lie on its surface, times its own albedo: texture
+ * and silhouettes come from the high planes, lighting from the low image.  All float32, no contraction, + - x /,
+ * floor, compares and selects only; "finite" and every dot product as above.  tests/upsample_model.py restates it.
+ *
+ * 8. Low pixel q: colour C_q and planes (A, id; N, t; P, flags)_q.  High pixel p = (x, y): planes (A, id; N, t;
+ *    P, flags)_p.  1 <= w <= W, 1 <= h <= H.  Parameters: pt_upsample_params.
+ *    Per low pixel q (a flat pass):
+ *     keep_q is pt_denoise's (its Prepare);  raw_q = every component of C_q is finite
+ *     F_q = the high pixels p with (xn_p, yn_p) = q (below) and id_p == id_q: q's footprint on its own primitive
+ *     D_q = 1 without DEMODULATE;  else, with d(A) = pt_denoise's divisor (A > 1/64 ? A : 1/64 per channel),
+ *           F_q empty:  d(A_q);   otherwise  (sum of d(A_p) over F_q, y outer, x inner, begun at 0) / (float)|F_q|
+ *     I_q = C_q / D_q
+ *    (pt_denoise divides a pixel's colour by its own albedo.  Here that is wrong wherever the albedo is textured: C_q is
+ *    the mean of albedo x light over the low pixel, A_q one sample of the albedo, and across a texture edge of contrast
+ *    50 : 1 the quotient is off by up to that factor, which every high pixel around q then inherits -- the guided
+ *    result measured worse than bilinear on a checker.  The high plane holds several samples of the albedo inside q, and
+ *    their mean is what C_q was multiplied by, to within their own sampling error.  With w = W, F_q = {q} and D_q = d(A_p).)
+ *    Per high pixel p:
+ *     sx = (float)w / (float)W;  u = ((float)x + 0.5f) * sx - 0.5f;  x0 = floor(u);  fx = u - x0
+ *     sy = (float)h / (float)H;  v = ((float)y + 0.5f) * sy - 0.5f;  y0 = floor(v);  fy = v - y0
+ *     xn = min((int)(((float)x + 0.5f) * sx), w - 1);  yn = min((int)(((float)y + 0.5f) * sy), h - 1)
+ *     guide_p = HIT && !EMISSIVE && every component of N_p, P_p finite
+ *     guide_p:
+ *       m = sigma_plane * t_p;  mm = m * m;  D_p = pt_denoise's divisor of A_p
+ *       ring 1:  sumW = 0, sumI = (0, 0, 0);  for j = 0, 1 (outer), i = 0, 1 (inner), q = (x0 + i, y0 + j):
+ *         b = (i ? fx : 1 - fx) * (j ? fy : 1 - fy)
+ *         the tap is skipped (by a select; its index is clamped into the low image before the load) when q is
+ *         outside the low image, when !keep_q, or when SAME_PRIMITIVE is set and id_q != id_p;  otherwise
+ *           w_n, w_p = rule 1's, of N_p, P_p, mm and N_q, P_q:
+ *             c = N_p . N_q;  c = c > 0 ? c : 0;  normal_power_log2 times: c = c * c;  w_n = c
+ *             g = N_p . (P_q - P_p);  w_p = 1 / (1 + (g * g) / mm)
+ *           wgt = (b * w_n) * w_p;   sumW = sumW + wgt;   sumI = sumI + wgt * I_q          (per channel)
+ *       sumW finite and > 0:  out_p.xyz = (sumI / sumW) * D_p
+ *       otherwise ring 2, with both sums begun again at 0:  for dy = -1 .. 2 (outer), dx = -1 .. 2 (inner), the four
+ *         taps of ring 1 left out, q = (x0 + dx, y0 + dy):
+ *         ex = (float)q.x - u;  ey = (float)q.y - v;  b = 1 / (1 + (ex * ex + ey * ey));  skips and weights as in ring 1
+ *         sumW finite and > 0:  out_p.xyz = (sumI / sumW) * D_p,  count_wide = count_wide + 1
+ *         otherwise            out_p.xyz = the words of C at (xn, yn),  count_nearest = count_nearest + 1
+ *     !guide_p (a miss, an emitter, a guide that is not finite): ring 1 on the raw colour, with b alone:
+ *         sumB = 0, sumC = (0, 0, 0);  the tap is skipped when q is outside the low image, when !raw_q, when keep_q,
+ *         when flags_q != flags_p (as bits), or, for an EMISSIVE p, when id_q != id_p;  otherwise
+ *           sumB = sumB + b;   sumC = sumC + b * C_q
+ *         sumB finite and > 0:  out_p.xyz = sumC / sumB;  otherwise the words of C at (xn, yn).  No demodulation
+ *         (the sky and the emitters have no albedo to divide by) and no count.
+ *     out_p.w = 1
+ *    A kept pixel never reaches an unguided one and the other way round, and a pixel that is not finite reaches none.
+ *    With w = W and h = H: sx = 1, u = x exactly, fx = 0, so ring 1 has one tap of b = 1 (q = p) and three of b = 0.
+ *    A kept p then gives (((1 * w_n) * w_p) * I_p / ((1 * w_n) * w_p)) * D_p with w_n = (N_p . N_p)^(2^power) and
+ *    w_p = 1: C_p to within four roundings (I_p's division, the product, the quotient and the demodulation), not the identity; where
+ *    w_n underflows to 0 (a normal far from unit length) the pixel goes to ring 2.
+ *    Accepted: sigma_plane >= 1e-6 and finite, normal_power_log2 0..7, flags within PT_DENOISE_DEMODULATE |
+ *    PT_DENOISE_SAME_PRIMITIVE, staging 0..2 (pt_denoise's ranges); anything else (a NaN included) is PT_ERR_ARG and
+ *    the message names the field.
+ *    Two kernels: a flat pass over the low image forms D_q from the high plane 0 and packs what a tap needs into three float4, (I or C, class), (N, id),
+ *    (P, flags), class = 1 kept, 2 raw and not kept, 0 neither; upsample_kernel takes one high pixel per lane on the
+ *    filter's 32 x 8 tile, whose ring-1 footprint of at most 35 x 11 low texels is staged in LDS (staging 1) or read
+ *    through the caches (2); 0 = automatic.  Ring 2 and the nearest pixel are always read through the caches.  The
+ *    words are the same. */
+/* Defaults of the layers above (C++ Pathtracer::upsample, Python, the CLI's -upsample): sigma_plane and the normal
+ * power are pt_denoise's shipped values; both flags are set (the low pixel beside a silhouette is of one surface or
+ * the other, and the id keeps it from the wrong one). */
+#define PT_UPSAMPLE_DEFAULT_SIGMA_PLANE 0.005f
+#define PT_UPSAMPLE_DEFAULT_NORMAL_POWER_LOG2 3
+#define PT_UPSAMPLE_DEFAULT_FLAGS 3u
+typedef struct pt_upsample_params {
+    float sigma_plane;       /* relative to the hit distance of the high pixel */
+    uint32_t normal_power_log2;
+    uint32_t flags;          /* PT_DENOISE_DEMODULATE, PT_DENOISE_SAME_PRIMITIVE */
+    uint32_t staging;
+} pt_upsample_params;
+/* The image of `lo` that pt_upsample takes: the accumulation (pt_denoise's colour: * 1 / max(frames, 1), or / n per
+ * pixel while pt_holds_adaptive), or the held denoised, temporal or despiked image. */
+#define PT_UPSAMPLE_ACCUM 0u
+#define PT_UPSAMPLE_DENOISED 1u
+#define PT_UPSAMPLE_TEMPORAL 2u
+#define PT_UPSAMPLE_DESPIKED 3u
+
+/* Rule 8 from `lo`'s image and planes to `hi`'s planes; the result is held by `hi` (hi's width x height float4).
+ * `frames` is used by PT_UPSAMPLE_ACCUM only.  Refused, naming the reason: PT_ERR_ARG for the parameters, an unknown
+ * source, two contexts on different devices, a band partition on either context, and a `lo` larger than `hi` in either
+ * dimension; PT_ERR_STATE when the planes of either context are not current, or `lo` does not hold the source (a
+ * denoised image; a temporal image made from the planes it holds; a despiked image).  Errors are `hi`'s
+ * (pt_last_error(hi)).  Nothing of either context's render state is written, nothing at all of `lo` changes, and a
+ * refused call changes nothing.
+ * "An upsampled image is held" by `hi` from the end of this call until the next one begins (as the denoised image). */
+PT_API int pt_upsample(pt_context *hi, pt_context *lo, uint32_t source, uint32_t frames,
+                       const pt_upsample_params *params);
+/* 1 while an upsampled image is held, else 0 (a question, never an error). */
+PT_API int pt_holds_upsampled(const pt_context *ctx);
+/* The held upsampled image (rows x width float4, w = 1), its tonemap (pt_tonemap_denoised's arithmetic; RGBA8), the
+ * two counts (2 x uint32: guided pixels that needed ring 2, guided pixels that took the nearest low pixel) and the
+ * hipEvent times in ms of the two kernels (2 floats: the flat pass, upsample_kernel).  PT_ERR_STATE unless an upsampled
+ * image is held. */
+PT_API int pt_read_upsampled(pt_context *ctx, float *dst);
+PT_API int pt_tonemap_upsampled(pt_context *ctx, uint8_t *dst);
+PT_API int pt_read_upsample_counts(pt_context *ctx, uint32_t *dst);
+PT_API int pt_read_upsample_timing(pt_context *ctx, float *dst);
+/* Rule 8 on host arrays, without a context: color and lo_plane0..2 are lo_h x lo_w float4 (color's w is ignored),
+ * hi_plane0..2 and out are hi_h x hi_w float4, out_counts (optional) 2 x uint32.  Errors: pt_last_error(NULL). */
+PT_API int pt_upsample_image(int device, uint32_t lo_w, uint32_t lo_h, const float *color, const float *lo_plane0,
+                             const float *lo_plane1, const float *lo_plane2, uint32_t hi_w, uint32_t hi_h,
+                             const float *hi_plane0, const float *hi_plane1, const float *hi_plane2,
+                             const pt_upsample_params *params, float *out, uint32_t *out_counts);
+
 /* ---- Moving objects in the temporal passes --------------------------------------------------------
  * Rule 3 (temporal reprojection) and rule 4's first part (the step with moments) project one world point with
  * two cameras: only the camera may move.  Rule 7 is the same step when the objects moved too: a per-primitive

@@ -153,6 +153,12 @@ PT_API const float *pth_renderer_adaptive_variance(pth_renderer *r);
  * window's taps).  pth_renderer_despike_count: the pixels clamped, into *count. */
 PT_API int pth_renderer_despike(pth_renderer *r, const pt_despike_params *params);
 PT_API int pth_renderer_despike_count(pth_renderer *r, uint32_t *count);
+/* Pathtracer::upsample / upsampleCounts (pt_upsample, pt_read_upsample_counts, pt_hip.h; single device): `hi`
+ * reconstructs its frame from the image of `lo`.  source: PT_UPSAMPLE_*, or 0xffffffff = what lo's image calls return.
+ * Afterwards hi's image calls return the upsampled image, until its next render, filter call or scene change.
+ * pth_renderer_upsample_counts: the pixels that needed the wider ring and those that took the nearest low pixel. */
+PT_API int pth_renderer_upsample(pth_renderer *hi, pth_renderer *lo, uint32_t source, const pt_upsample_params *params);
+PT_API int pth_renderer_upsample_counts(pth_renderer *r, uint32_t *counts);
 PT_API float pth_renderer_timing(const pth_renderer *r);
 PT_API uint32_t pth_renderer_frames(const pth_renderer *r);
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer *r);

@@ -31,7 +31,7 @@ __all__ = ["Pathtracer", "Scene", "make_camera", "camera_rotate", "camera_transl
            "temporal_moments_image", "denoise_variance_image", "VARIANCE_DEFAULTS", "VDENOISE_DEFAULTS",
            "vfeedback_params", "denoise_variance_feedback_image", "VFEEDBACK_DEFAULTS", "adaptive_variance_params",
            "adaptive_variance_image", "AVARIANCE_DEFAULTS", "ADENOISE_SIGMA_L", "despike_params", "despike_image",
-           "DESPIKE_DEFAULTS", "motion_table", "temporal_motion_image", "temporal_moments_motion_image", "NO_PREVIOUS"]
+           "DESPIKE_DEFAULTS", "upsample_params", "upsample_image", "UPSAMPLE_DEFAULTS", "UPSAMPLE_SOURCES", "motion_table", "temporal_motion_image", "temporal_moments_motion_image", "NO_PREVIOUS"]
 
 HITTABLE_TYPES = ["SPHERE", "CYLINDER", "DISK", "CONE", "PARABOLOID", "QUAD", "CUBE"]   # Hittable.h:9-12
 MATERIAL_TYPES = ["LAMBERT", "GGX", "LAMBERT_GGX"]                                     # Material.h:9-12
@@ -614,6 +614,61 @@ def despike_image(color, plane0, plane1, plane2, radius: Optional[int] = None, r
     return (out, int(count.value)) if return_count else out
 
 
+# Defaults of the guided upsampling (PT_UPSAMPLE_DEFAULT_* of include/pt_hip.h): sigma_plane and the
+# normal power are the a-trous filter's, and both flags are set.
+UPSAMPLE_DEFAULTS = {"sigma_plane": 0.005, "normal_power_log2": 3, "demodulate": True, "same_primitive": True}
+# upsample(source=...): the image of the low-resolution Pathtracer that is taken (PT_UPSAMPLE_* of include/pt_hip.h)
+UPSAMPLE_SOURCES = {"accum": N.PT_UPSAMPLE_ACCUM, "denoised": N.PT_UPSAMPLE_DENOISED, "temporal": N.PT_UPSAMPLE_TEMPORAL,
+                    "despiked": N.PT_UPSAMPLE_DESPIKED}
+
+
+def upsample_params(sigma_plane: Optional[float] = None, normal_power_log2: Optional[int] = None,
+                    demodulate: Optional[bool] = None, same_primitive: Optional[bool] = None,
+                    staging: int = 0) -> "N.PtUpsampleParams":
+    """pt_upsample_params from keyword arguments, refused here (PT_ERR_ARG naming the field) before any device call
+    when a value is outside the accepted range of include/pt_hip.h."""
+    d = UPSAMPLE_DEFAULTS
+    sigma_plane = d["sigma_plane"] if sigma_plane is None else sigma_plane
+    normal_power_log2 = d["normal_power_log2"] if normal_power_log2 is None else normal_power_log2
+    demodulate = d["demodulate"] if demodulate is None else demodulate
+    same_primitive = d["same_primitive"] if same_primitive is None else same_primitive
+    sp = np.float32(sigma_plane)
+    if not (sp >= np.float32(1e-6) and np.isfinite(sp)):
+        raise _refuse(f"upsample: sigma_plane must be >= 1e-6 and finite, not {sigma_plane!r}")
+    n = normal_power_log2
+    if isinstance(n, float) and not np.isfinite(n) or int(n) != n or not 0 <= int(n) <= 7:
+        raise _refuse(f"upsample: normal_power_log2 must be 0..7, not {normal_power_log2!r}")
+    if staging not in (0, 1, 2):
+        raise _refuse(f"upsample: staging must be 0, 1 or 2, not {staging!r}")
+    flags = (N.PT_DENOISE_DEMODULATE if demodulate else 0) | (N.PT_DENOISE_SAME_PRIMITIVE if same_primitive else 0)
+    return N.PtUpsampleParams(float(sp), int(n), flags, int(staging))
+
+
+def upsample_image(color, lo_plane0, lo_plane1, lo_plane2, hi_plane0, hi_plane1, hi_plane2,
+                   sigma_plane: Optional[float] = None, normal_power_log2: Optional[int] = None,
+                   demodulate: Optional[bool] = None, same_primitive: Optional[bool] = None, staging: int = 0,
+                   device: int = 0, return_counts: bool = False):
+    """pt_upsample_image: the guided upsampling (rule 8 of include/pt_hip.h) on host arrays, without a Pathtracer:
+    the colour and the three feature planes of a low image (h x w x 4 float32) and the three planes of the full frame
+    (H x W x 4, w <= W and h <= H).  Returns H x W x 4, or (image, (pixels that needed the wider ring, pixels that took
+    the nearest low pixel)) with return_counts."""
+    params = upsample_params(sigma_plane, normal_power_log2, demodulate, same_primitive, staging)
+    c = _image4("color", color)
+    lows = [_image4(f"lo_plane{k}", p, c.shape) for k, p in enumerate((lo_plane0, lo_plane1, lo_plane2))]
+    h0 = _image4("hi_plane0", hi_plane0)
+    highs = [h0] + [_image4(f"hi_plane{k + 1}", p, h0.shape) for k, p in enumerate((hi_plane1, hi_plane2))]
+    if c.shape[0] > h0.shape[0] or c.shape[1] > h0.shape[1]:
+        raise _refuse(f"upsample_image: the low image {c.shape[:2]} is larger than the high planes {h0.shape[:2]}")
+    out = np.zeros_like(h0)
+    counts = (C.c_uint32 * 2)()
+    fp = C.POINTER(C.c_float)
+    rc = N.hip().pt_upsample_image(int(device), c.shape[1], c.shape[0], c.ctypes.data_as(fp),
+                                   *[p.ctypes.data_as(fp) for p in lows], h0.shape[1], h0.shape[0],
+                                   *[p.ctypes.data_as(fp) for p in highs], C.byref(params), out.ctypes.data_as(fp), counts)
+    N.check_ctx(rc, None)
+    return (out, (int(counts[0]), int(counts[1]))) if return_counts else out
+
+
 class Scene:
     """A parsed scene file (no GPU): objects in file order, the SAH BVH, camera, textures."""
 
@@ -1019,6 +1074,60 @@ class Pathtracer:
         ms = (C.c_float * 2)()
         N.check_ctx(N.hip().pt_read_despike_timing(self._ctx, ms), self._ctx)
         return {"prepare": float(ms[0]), "despike": float(ms[1])}
+
+    # --- guided upsampling of a low-resolution render (pt_upsample; rule 8 of pt_hip.h) ----------------
+    def upsample(self, lo: "Pathtracer", source: str = "accum", frames: Optional[int] = None,
+                 sigma_plane: Optional[float] = None, normal_power_log2: Optional[int] = None,
+                 demodulate: Optional[bool] = None, same_primitive: Optional[bool] = None, staging: int = 0) -> np.ndarray:
+        """Reconstruct this Pathtracer's frame from the image of `lo`, a Pathtracer of the same scene and camera at a
+        lower resolution (include/pt_hip.h, rule 8): every pixel takes the demodulated colour of the low pixels around
+        it that lie on its surface, times its own albedo.  Both need the planes of a features(camera) call; this one
+        needs no render.  source: "accum" (lo's render, over `frames`, default lo.frames), "denoised", "temporal" or
+        "despiked" (what lo holds).  Returns rows x width x 4 float32 and leaves both render states as they are.
+        Arguments out of range raise before any device call."""
+        self._single("upsample")
+        params = upsample_params(sigma_plane, normal_power_log2, demodulate, same_primitive, staging)
+        if source not in UPSAMPLE_SOURCES:
+            raise _refuse(f"upsample: source must be 'accum', 'denoised', 'temporal' or 'despiked', not {source!r}")
+        if not isinstance(lo, Pathtracer):
+            raise _refuse(f"upsample: lo must be a Pathtracer, not {type(lo).__name__}")
+        lo._single("upsample")
+        if frames is not None and source != "accum":
+            raise _refuse(f"upsample: frames is not used with source={source!r} (the held image has been divided already)")
+        f = lo.frames if frames is None else int(frames)
+        if not 0 <= f <= 0xffffffff:
+            raise _refuse(f"upsample: frames must be 0..2^32 - 1, not {frames!r}")
+        N.check_ctx(N.hip().pt_upsample(self._ctx, lo._ctx, UPSAMPLE_SOURCES[source], f, C.byref(params)), self._ctx)
+        return self.upsampled()
+
+    def upsampled(self) -> np.ndarray:
+        """The held upsampled image again (pt_read_upsampled): until the next upsample() begins."""
+        self._single("upsampled")
+        out = np.zeros((self.rows, self.width, 4), dtype=np.float32)
+        N.check_ctx(N.hip().pt_read_upsampled(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float))), self._ctx)
+        return out
+
+    def tonemap_upsampled(self) -> np.ndarray:
+        """The held upsampled image through the tonemap (RGBA8, rows x width)."""
+        self._single("tonemap_upsampled")
+        out = np.zeros((self.rows, self.width, 4), dtype=np.uint8)
+        N.check_ctx(N.hip().pt_tonemap_upsampled(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint8))), self._ctx)
+        return out
+
+    def upsample_counts(self) -> Dict[str, int]:
+        """Of the last upsample(): {"wide": guided pixels that needed the second ring, "nearest": guided pixels no tap
+        of either ring served, which took the nearest low pixel} (pt_read_upsample_counts)."""
+        self._single("upsample_counts")
+        n = (C.c_uint32 * 2)()
+        N.check_ctx(N.hip().pt_read_upsample_counts(self._ctx, n), self._ctx)
+        return {"wide": int(n[0]), "nearest": int(n[1])}
+
+    def upsample_timing(self) -> Dict[str, float]:
+        """Kernel times of the last upsample() in ms (hipEvents): {"prepare", "upsample"}."""
+        self._single("upsample_timing")
+        ms = (C.c_float * 2)()
+        N.check_ctx(N.hip().pt_read_upsample_timing(self._ctx, ms), self._ctx)
+        return {"prepare": float(ms[0]), "upsample": float(ms[1])}
 
     def adaptive_variance(self) -> np.ndarray:
         """The per-pixel variance the last denoise(guide="adaptive") made (pt_read_adaptive_variance): rows x width

@@ -103,6 +103,13 @@ class PtDespikeParams(C.Structure):
                 ("flags", C.c_uint32), ("staging", C.c_uint32)]
 
 
+class PtUpsampleParams(C.Structure):
+    """pt_upsample_params (pt_hip.h, the guided upsampling)."""
+    _fields_ = [("sigma_plane", C.c_float), ("normal_power_log2", C.c_uint32), ("flags", C.c_uint32),
+                ("staging", C.c_uint32)]
+
+
+PT_UPSAMPLE_ACCUM, PT_UPSAMPLE_DENOISED, PT_UPSAMPLE_TEMPORAL, PT_UPSAMPLE_DESPIKED = 0, 1, 2, 3
 PT_FEATURE_HIT, PT_FEATURE_EMISSIVE = 1, 2
 PT_TEMPORAL_DEMODULATE, PT_TEMPORAL_SAME_PRIMITIVE = 1, 2
 PT_DENOISE_DEMODULATE, PT_DENOISE_SAME_PRIMITIVE = 1, 2
@@ -206,6 +213,14 @@ _HIP_SYMBOLS = {
     "pt_denoise_despiked": (C.c_int, [C.c_void_p, P(PtDenoiseParams)]),
     "pt_despike_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 4
                          + [P(PtDespikeParams), P(C.c_float), P(C.c_uint32)]),
+    "pt_upsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(PtUpsampleParams)]),
+    "pt_holds_upsampled": (C.c_int, [C.c_void_p]),
+    "pt_read_upsampled": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_tonemap_upsampled": (C.c_int, [C.c_void_p, P(C.c_uint8)]),
+    "pt_read_upsample_counts": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
+    "pt_read_upsample_timing": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_upsample_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 4 + [C.c_uint32, C.c_uint32]
+                          + [P(C.c_float)] * 3 + [P(PtUpsampleParams), P(C.c_float), P(C.c_uint32)]),
     "pt_set_scene_moved": (C.c_int, [C.c_void_p, P(PtBvhNode), C.c_uint32, P(PtHittable), C.c_uint32, P(C.c_float),
                                      P(C.c_uint32)]),
     "pt_holds_motion": (C.c_int, [C.c_void_p]),
@@ -277,6 +292,8 @@ _HOST_SYMBOLS = {
     "pth_renderer_adaptive_variance": (P(C.c_float), [C.c_void_p]),
     "pth_renderer_despike": (C.c_int, [C.c_void_p, P(PtDespikeParams)]),
     "pth_renderer_despike_count": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
+    "pth_renderer_upsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, P(PtUpsampleParams)]),
+    "pth_renderer_upsample_counts": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
     "pth_renderer_timing": (C.c_float, [C.c_void_p]),
     "pth_renderer_frames": (C.c_uint32, [C.c_void_p]),
     "pth_renderer_local_rows": (C.c_uint32, [C.c_void_p]),

@@ -21,6 +21,9 @@
 //                  neighbours is scaled down to their level (Pathtracer::renderFeatures + despike, the parameters
 //                  at their defaults).  With -denoise the filter runs on the despiked image.  One GPU; not with
 //                  -denoise_guide adaptive, whose variance describes the unclamped colour.
+//   -upsample K    K = 2..4: trace (and -despike / -denoise) at ceil(w / K) x ceil(h / K), take the first-hit features at
+//                  both sizes and reconstruct the w x h image from them (Pathtracer::upsample, rule 8 of pt_hip.h).
+//                  One GPU; not with -denoise_guide adaptive.
 // The windowed / interactive mode (-window, -enable_controls) is not supported.
 #include <algorithm>
 #include <cstdio>
@@ -108,6 +111,16 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
             continue;
         }
         if (strcmp(argv[i], "-despike") == 0) { params.m_despike = true; ++i; continue; }
+        if (strcmp(argv[i], "-upsample") == 0) {
+            char* end = nullptr;
+            const long k = i + 1 < argc ? strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || k < 2 || k > 4) {
+                printf("Invalid input for -upsample! (a factor of 2..4)\n");
+                displayHelp = true;
+            } else params.m_upsample = (unsigned int)k;
+            i += 2;
+            continue;
+        }
         if (strcmp(argv[i], "-minspp") == 0) { uintArg(i, "-minspp", params.m_minSpp); i += 2; continue; }
         printf("Can't parse argument: %s\n", argv[i]);
         displayHelp = true;
@@ -119,6 +132,10 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
     }
     if (params.m_despike && params.m_denoiseAdaptive) {
         printf("Invalid input for -despike! (not with -denoise_guide adaptive)\n");
+        displayHelp = true;
+    }
+    if (params.m_upsample && params.m_denoiseAdaptive) {
+        printf("Invalid input for -upsample! (not with -denoise_guide adaptive)\n");
         displayHelp = true;
     }
     // (`pathtracer -help` alone lists the options: the lone argument is not an input file)
@@ -150,6 +167,8 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
         printf("%-30s With -adaptive and -denoise: guide the filter by the adaptive render's own per-pixel variance\n",
                "-denoise_guide adaptive");
         printf("%-30s Clamp fireflies before writing (and before -denoise): same-surface neighbourhood limit\n", "-despike");
+        printf("%-30s Trace at 1/K of the width and height, K = 2..4, and reconstruct the image from full-size features\n",
+               "-upsample K");
         return false;
     }
     params.m_enableControls = params.m_enableControls && params.m_showWindow;
@@ -192,14 +211,25 @@ int main(int argc, char* argv[])
         printf("-despike renders on one GPU; ignoring -gpus.\n");
         gpus = 1;
     }
+    if (params.m_upsample && gpus > 1) {
+        printf("-upsample renders on one GPU; ignoring -gpus.\n");
+        gpus = 1;
+    }
     if (adaptive && gpus > 1) {
         printf("-adaptive renders on one GPU; ignoring -gpus.\n");
         gpus = 1;
     }
     // main.cpp:263 constructs one Pathtracer on device 0; -gpus N spans N devices with the same
     // interface (row bands over the devices, RCCL gather to device 0 when the image is read)
-    std::unique_ptr<Pathtracer> pathtracer;
-    if (gpus == 1) {
+    // -upsample K: `pathtracer` is the low-resolution one, which everything up to the filters runs on, and `full` the
+    // one of the image's size, which only takes features and reconstructs (the camera is the image's: its aspect)
+    std::unique_ptr<Pathtracer> pathtracer, full;
+    const uint32_t K = params.m_upsample;
+    if (K) {
+        pathtracer.reset(new Pathtracer((params.m_width + K - 1) / K, (params.m_height + K - 1) / K));
+        full.reset(new Pathtracer(params.m_width, params.m_height));
+        loadScene(*full, params);
+    } else if (gpus == 1) {
         pathtracer.reset(new Pathtracer(params.m_width, params.m_height));
     } else {
         std::vector<int> devices(gpus);
@@ -255,6 +285,17 @@ int main(int argc, char* argv[])
         if (!params.m_despike) pathtracer->renderFeatures(camera);     // (a features call would end the despiked image)
         const float sigma = pathtracer->denoise(options);
         printf("Denoised: %u a-trous iterations, colour sigma %g\n", options.iterations, sigma);
+    }
+
+    if (K) {
+        if (!params.m_despike && !params.m_denoise) pathtracer->renderFeatures(camera);
+        full->renderFeatures(camera);
+        full->upsample(*pathtracer);
+        uint32_t counts[2] = {0, 0};
+        full->upsampleCounts(counts);
+        printf("Upsampled: %u x %u from %u x %u, %u pixels from the wider ring, %u from the nearest pixel\n", params.m_width,
+               params.m_height, (params.m_width + K - 1) / K, (params.m_height + K - 1) / K, counts[0], counts[1]);
+        pathtracer = std::move(full);
     }
 
     if (params.m_outputFilepath) {

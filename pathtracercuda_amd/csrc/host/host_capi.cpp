@@ -518,6 +518,31 @@ PT_API int pth_renderer_despike(pth_renderer* r, const pt_despike_params* params
     PTH_GUARD_END
 }
 
+PT_API int pth_renderer_upsample(pth_renderer* hi, pth_renderer* lo, uint32_t source, const pt_upsample_params* params)
+{
+    if (!hi || !lo || !params) return setError(PT_ERR_ARG, "invalid argument");
+    pth_renderer* r = hi;
+    PTH_GUARD_BEGIN
+    Pathtracer::UpsampleOptions o;
+    o.source = source;
+    o.sigmaPlane = params->sigma_plane;
+    o.normalPowerLog2 = params->normal_power_log2;
+    o.flags = params->flags;
+    o.staging = params->staging;
+    r->pt->upsample(*lo->pt, o);
+    return PT_OK;
+    PTH_GUARD_END
+}
+
+PT_API int pth_renderer_upsample_counts(pth_renderer* r, uint32_t* counts)
+{
+    if (!r || !counts) return setError(PT_ERR_ARG, "invalid argument");
+    PTH_GUARD_BEGIN
+    r->pt->upsampleCounts(counts);
+    return PT_OK;
+    PTH_GUARD_END
+}
+
 PT_API int pth_renderer_despike_count(pth_renderer* r, uint32_t* count)
 {
     if (!r || !count) return setError(PT_ERR_ARG, "invalid argument");

@@ -111,6 +111,7 @@ void Pathtracer::setScene(size_t count, const CpuHittable* hittables)
     m_hittableCount = (uint32_t)dp.size();
     m_denoised = false;
     m_despiked = false;
+    m_upsampled = false;
     rememberScene(count, hittables);
     m_motionRows.clear();
     m_motionPrev.clear();
@@ -207,6 +208,7 @@ void Pathtracer::setSceneMoved(size_t count, const CpuHittable* hittables, const
     m_hittableCount = (uint32_t)dp.size();
     m_denoised = false;
     m_despiked = false;
+    m_upsampled = false;
 }
 
 bool Pathtracer::holdsMotion() const { return !m_group && pt_holds_motion(m_ctx) != 0; }
@@ -233,6 +235,7 @@ void Pathtracer::renderChunks(const Camera& camera, uint32_t spp, uint32_t chunk
     m_adaptive = adaptive();
     m_denoised = false;
     m_despiked = false;
+    m_upsampled = false;
     if (ignoreHistory) m_accumulatedFrames = 0;
     m_timing = ms;
     m_accumulatedFrames += chunks;
@@ -256,6 +259,7 @@ Pathtracer::AdaptiveResult Pathtracer::renderAdaptive(const Camera& camera, uint
     m_adaptive = true;
     m_denoised = false;
     m_despiked = false;
+    m_upsampled = false;
     m_accumulatedFrames = 0;          // the per-pixel counts describe the buffer now
     return AdaptiveResult{res.rounds, res.samples, res.gpu_ms};
 }
@@ -321,6 +325,7 @@ float Pathtracer::denoise(const DenoiseOptions& o)
     if (despiked()) check(pt_denoise_despiked(m_ctx, &p), "pt_denoise_despiked");
     else check(pt_denoise(m_ctx, m_accumulatedFrames, &p), "pt_denoise");
     m_denoised = true;
+    m_upsampled = false;
     return p.sigma_color;
 }
 
@@ -334,12 +339,33 @@ void Pathtracer::despike(const DespikeOptions& o)
     const pt_despike_params p = {o.radius, o.rank, o.factor, o.floor, minNeighbors, o.sigmaPlane, o.normalCosMin, o.flags, o.staging};
     check(pt_despike(m_ctx, m_accumulatedFrames, &p), "pt_despike");
     m_despiked = true;
+    m_upsampled = false;
     m_denoised = false;               // a denoised image was of the image before the clamp
 }
 
 // m_despiked says that this class made a despiked image and has ended it nowhere; the device context says whether
 // it is still held (a call on the context, past this class, ends it too)
 bool Pathtracer::despiked() const { return m_despiked && !m_group && pt_holds_despiked(m_ctx) != 0; }
+
+void Pathtracer::upsample(Pathtracer& lo, const UpsampleOptions& o)
+{
+    if (m_group || lo.m_group) check(PT_ERR_STATE, "upsample: not available on a device group");
+    uint32_t source = o.source;
+    if (source == kUpsampleAuto)
+        source = lo.m_denoised ? PT_UPSAMPLE_DENOISED : (lo.despiked() ? PT_UPSAMPLE_DESPIKED : PT_UPSAMPLE_ACCUM);
+    const pt_upsample_params p = {o.sigmaPlane, o.normalPowerLog2, o.flags, o.staging};
+    check(pt_upsample(m_ctx, lo.m_ctx, source, lo.m_accumulatedFrames, &p), "pt_upsample");
+    m_upsampled = true;
+}
+
+// (as despiked(): the class's flag and the context's fact)
+bool Pathtracer::upsampled() const { return m_upsampled && !m_group && pt_holds_upsampled(m_ctx) != 0; }
+
+void Pathtracer::upsampleCounts(uint32_t counts[2])
+{
+    if (m_group) check(PT_ERR_STATE, "upsampleCounts: not available on a device group");
+    check(pt_read_upsample_counts(m_ctx, counts), "pt_read_upsample_counts");
+}
 
 uint32_t Pathtracer::despikeCount()
 {
@@ -390,6 +416,7 @@ void Pathtracer::denoiseVariance(const VarianceDenoiseOptions& o)
     const pt_vdenoise_params p = {o.iterations, o.sigmaL, o.varianceFloor, o.sigmaPlane, o.normalPowerLog2, o.flags, o.staging};
     check(pt_denoise_variance(m_ctx, &p), "pt_denoise_variance");
     m_denoised = true;
+    m_upsampled = false;
 }
 
 void Pathtracer::denoiseVariance(const VarianceDenoiseOptions& o, uint32_t feedbackLevel)
@@ -399,6 +426,7 @@ void Pathtracer::denoiseVariance(const VarianceDenoiseOptions& o, uint32_t feedb
     const pt_vfeedback_params f = {feedbackLevel};
     check(pt_denoise_variance_feedback(m_ctx, &p, &f), "pt_denoise_variance_feedback");
     m_denoised = true;
+    m_upsampled = false;
 }
 
 void Pathtracer::denoiseAdaptive(const AdaptiveVarianceOptions& a, const VarianceDenoiseOptions& o)
@@ -408,6 +436,7 @@ void Pathtracer::denoiseAdaptive(const AdaptiveVarianceOptions& a, const Varianc
     const pt_vdenoise_params p = {o.iterations, o.sigmaL, o.varianceFloor, o.sigmaPlane, o.normalPowerLog2, o.flags, o.staging};
     check(pt_denoise_adaptive(m_ctx, &v, &p), "pt_denoise_adaptive");
     m_denoised = true;
+    m_upsampled = false;
 }
 
 const float* Pathtracer::adaptiveVariance()
@@ -456,12 +485,13 @@ uint32_t Pathtracer::loadTexture(const char* path)
     ++m_textureCount;
     m_textureKeys.push_back({w, h, hash});
     m_despiked = false;
+    m_upsampled = false;
     return m_textureCount;
 }
 
 void Pathtracer::setSkyboxTextureHandle(uint32_t handle)
 {
-    if (handle != m_skyboxTextureHandle) m_despiked = false;     // the image's colours are of the old sky
+    if (handle != m_skyboxTextureHandle) m_despiked = m_upsampled = false;     // the image's colours are of the old sky
     m_skyboxTextureHandle = handle;
     if (m_group) check(pt_group_set_skybox(m_group, handle), "pt_group_set_skybox");
     else check(pt_set_skybox(m_ctx, handle), "pt_set_skybox");
@@ -469,6 +499,10 @@ void Pathtracer::setSkyboxTextureHandle(uint32_t handle)
 
 float* Pathtracer::getHDRImageData()
 {
+    if (upsampled()) {
+        check(pt_read_upsampled(m_ctx, m_cpuAccumBuffer.data()), "pt_read_upsampled");
+        return m_cpuAccumBuffer.data();
+    }
     if (m_denoised) {
         check(pt_read_denoised(m_ctx, m_cpuAccumBuffer.data()), "pt_read_denoised");
         return m_cpuAccumBuffer.data();
@@ -494,6 +528,10 @@ float* Pathtracer::getHDRImageData()
 
 char* Pathtracer::getImageData()
 {
+    if (upsampled()) {
+        check(pt_tonemap_upsampled(m_ctx, (uint8_t*)m_cpuResultBuffer.data()), "pt_tonemap_upsampled");
+        return m_cpuResultBuffer.data();
+    }
     if (m_denoised) {
         check(pt_tonemap_denoised(m_ctx, (uint8_t*)m_cpuResultBuffer.data()), "pt_tonemap_denoised");
         return m_cpuResultBuffer.data();

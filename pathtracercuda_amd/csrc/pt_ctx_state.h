@@ -1,6 +1,6 @@
 // pt_ctx_state.h -- what a context carries from one call to the next, and every rule that moves it:
 // no HIP call, no context, plain values.  The C ABI functions (pt_kernels.hip, pt_denoise.h, pt_temporal.h, pt_svgf.h,
-// pt_adaptive_variance.h, pt_despike.h)
+// pt_adaptive_variance.h, pt_despike.h, pt_upsample.h)
 // raise the events below and ask the predicates; they assign none of these fields themselves.
 // tools/ctx_state_check.cpp and tests/test_ctx_state.py run the same functions on the CPU.
 //
@@ -55,6 +55,10 @@
 //                   by a sky change to another handle, and by a second scene_moved (one move per temporal step: the
 //                   two tables would have to be composed, so the history ends with it).  A render, a camera change,
 //                   an RNG write and a features call end nothing.  Implies histValid.
+//   usValid         an upsampled image is held (pt_read_upsampled, its tonemap, counts and timing), by the context of the
+//                   larger frame: ended when a pt_upsample has passed its checks, set when it is done (dnValid's rule: the
+//                   image is a result handed out, and what it was made from may move on).  Nothing else ends it, and
+//                   the context of the smaller frame raises no event.
 //   epoch           counts the launches that wrote the accumulation (a device group's gather cache
 //                   key, pt_group.h).  Never decreases.
 // A call refused for its arguments or for the state raises no event (but for a render whose plan is a
@@ -81,6 +85,7 @@ struct CtxState {
     bool avValid = false;
     bool dsValid = false;
     bool motionValid = false;
+    bool usValid = false;
     uint64_t epoch = 0;
 };
 
@@ -235,6 +240,8 @@ inline void adaptive_variance_done(CtxState& s) { s.avValid = s.adCountsValid; }
 inline void despike_begins(CtxState& s) { s.dsValid = false; }
 // (pt_despike has checked planes_current, and nothing between its two events can end the planes)
 inline void despike_done(CtxState& s) { s.dsValid = s.featValid; }
+inline void upsample_begins(CtxState& s) { s.usValid = false; }
+inline void upsample_done(CtxState& s) { s.usValid = true; }
 
 // ---- predicates -----------------------------------------------------------------------------------
 inline bool counts_describe_buffer(const CtxState& s) { return s.adCountsValid; }
@@ -248,5 +255,6 @@ inline bool history_has_moments(const CtxState& s) { return s.momValid; }
 inline bool variance_of_counts(const CtxState& s) { return s.avValid; }
 inline bool holds_despiked(const CtxState& s) { return s.dsValid; }
 inline bool holds_motion(const CtxState& s) { return s.motionValid; }
+inline bool holds_upsampled(const CtxState& s) { return s.usValid; }
 
 } // namespace pt

@@ -453,6 +453,8 @@ __global__ void __launch_bounds__(256) adapt_scatter_kernel(const unsigned long 
 
 #include "pt_dev_despike.h"
 
+#include "pt_dev_upsample.h"
+
 // Multi-device gather, second half: scatter one device's received rows (its bands, in local row
 // order) into the full image.  A band is band-rows consecutive image rows in both buffers, so every
 // lane copies one float4 of a coalesced row.
@@ -576,6 +578,12 @@ struct pt_context {
     hipEvent_t dsEv[3] = {};          // before the flat pass, between the kernels, after despike_kernel
     float dsMs[2] = {};
     uint32_t dsCount = 0;
+    // guided upsampling (pt_upsample.h), held by the context of the larger frame; no render state
+    float4* usBuf = nullptr;          // [3][usLoCap] the packed low texels, [usLoCap] the low colour, [pixels] the upsampled image, the counts
+    size_t usLoCap = 0;               // low pixels the buffers were made for
+    hipEvent_t usEv[3] = {};          // before the flat pass, between the kernels, after upsample_kernel
+    float usMs[2] = {};
+    uint32_t usCounts[2] = {};        // guided pixels that needed ring 2, that took the nearest low pixel
     std::string err;
 };
 
@@ -885,6 +893,7 @@ PT_API void pt_destroy(pt_context* ctx)
     (void)hipFree(ctx->motion);
     (void)hipFree(ctx->avBuf);
     (void)hipFree(ctx->dsBuf);
+    (void)hipFree(ctx->usBuf);
     for (auto& e : ctx->dnEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->tmEv)
@@ -894,6 +903,8 @@ PT_API void pt_destroy(pt_context* ctx)
     for (auto& e : ctx->avEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->dsEv)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : ctx->usEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& t : ctx->hostTex) (void)hipFree((void*)t.texels);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -2073,6 +2084,8 @@ PT_API int pt_set_kernel_variant(pt_context* ctx, int variant)
 #include "pt_adaptive_variance.h"
 
 #include "pt_despike.h"
+
+#include "pt_upsample.h"
 
 extern "C" PT_API const char* pt_last_error(const pt_context* ctx)
 {

@@ -44,12 +44,13 @@ static void (*const kEventFns[])(CtxState&) = {
     scene_or_texture_changed, rng_written, schedule_changed, order_dropped, order_replaced, order_biased,
     accum_written, stash_made, adaptive_begins, adaptive_done, features_begin, features_done, denoise_begins, denoise_done,
     temporal_begins, temporal_done, moments_done, adaptive_variance_begins, adaptive_variance_done, despike_begins,
-    despike_done, scene_moved};
+    despike_done, scene_moved, upsample_begins, upsample_done};
 static const char* const kEventNames[] = {
     "scene_or_texture_changed", "rng_written", "schedule_changed", "order_dropped", "order_replaced",
     "order_biased", "accum_written", "stash_made", "adaptive_begins", "adaptive_done", "features_begin", "features_done",
     "denoise_begins", "denoise_done", "temporal_begins", "temporal_done", "moments_done", "adaptive_variance_begins",
-    "adaptive_variance_done", "despike_begins", "despike_done", "scene_moved"};
+    "adaptive_variance_done", "despike_begins", "despike_done", "scene_moved", "upsample_begins",
+    "upsample_done"};
 constexpr int kEvents = sizeof(kEventFns) / sizeof(kEventFns[0]);
 // the tool's own list of the events after which a sample is no longer what the last render's was
 static bool moves_epoch(void (*event)(CtxState&))
@@ -60,10 +61,10 @@ static_assert(kEvents == sizeof(kEventNames) / sizeof(kEventNames[0]), "one name
 
 static bool (*const kPredicates[])(const CtxState&) = {counts_describe_buffer, moments_continue, planes_current, holds_denoised,
                                                        holds_temporal, history_held, temporal_of_planes, history_has_moments,
-                                                       variance_of_counts, holds_despiked, holds_motion};
+                                                       variance_of_counts, holds_despiked, holds_motion, holds_upsampled};
 static const char* const kPredicateNames[] = {"counts_describe_buffer", "moments_continue", "planes_current", "holds_denoised",
                                               "holds_temporal", "history_held", "temporal_of_planes", "history_has_moments",
-                                              "variance_of_counts", "holds_despiked", "holds_motion"};
+                                              "variance_of_counts", "holds_despiked", "holds_motion", "holds_upsampled"};
 constexpr int kPredicateCount = sizeof(kPredicates) / sizeof(kPredicates[0]);
 static_assert(kPredicateCount == sizeof(kPredicateNames) / sizeof(kPredicateNames[0]), "one name per predicate");
 
@@ -95,6 +96,7 @@ struct Fuzz {
         const bool av = s.avValid, counts = s.adCountsValid;
         const bool ds = s.dsValid, feat = s.featValid;
         const bool motion = s.motionValid;
+        const bool us = s.usValid;
         const uint32_t e = next() % (kEvents + 6);       // (a render as likely as four other events)
         if (e < (uint32_t)kEvents) {
             kEventFns[e](s);
@@ -151,13 +153,17 @@ struct Fuzz {
             // (another sky is checked above), a second move; only a first move over a held history sets it
             const bool endsMotion = f == temporal_begins || f == scene_or_texture_changed;
             check(s.motionValid == (f == scene_moved ? (hist && !motion) : (motion && !endsMotion)));
+            // the tool's own list for the upsampled image: only the call's own two events move it
+            check(s.usValid == (f == upsample_done ? true : (us && f != upsample_begins)));
             if (f == scene_moved) check(!s.featValid && s.stateEpoch == stateEpoch + 1 && s.order.stale);
         } else if (e != (uint32_t)kEvents + 1) {
             check(s.histValid == hist && s.momValid == mom);     // a sort of the order, a render
             check(s.motionValid == motion);
+            check(s.usValid == us);                              // (a render ends no upsampled image)
             if (e == (uint32_t)kEvents) check(s.avValid == av && s.dsValid == ds);
         } else {
             check(s.avValid == av);                              // a sky ends no variance of the counts
+            check(s.usValid == us);                              // nor an upsampled image
         }
         check(s.stateEpoch >= stateEpoch && s.epoch >= epoch);
         check(s.aheadMisses <= 1000u);
@@ -170,12 +176,12 @@ static void print_state(const CtxState& s, const std::string& extra)
            "\"lastState\": %llu, \"launched\": %d, \"lastCam\": %d, \"aheadValid\": %d, \"aheadMisses\": %u, \"adMomValid\": %d, "
            "\"adCountsValid\": %d, \"featValid\": %d, \"dnValid\": %d, \"tpValid\": %d, \"histValid\": %d, "
            "\"tpOfPlanes\": %d, \"momValid\": %d, \"avValid\": %d, \"dsValid\": %d, \"motionValid\": %d, "
-           "\"epoch\": %llu%s}\n",
+           "\"usValid\": %d, \"epoch\": %llu%s}\n",
            (int)s.order.valid, (int)s.order.stale, (unsigned long long)s.order.samples, s.order.strip,
            (unsigned long long)s.stateEpoch, (unsigned long long)s.lastState, (int)s.launched, (int)s.lastCam.origin[0],
            (int)s.aheadValid, s.aheadMisses, (int)s.adMomValid, (int)s.adCountsValid, (int)s.featValid, (int)s.dnValid,
            (int)s.tpValid, (int)s.histValid, (int)s.tpOfPlanes, (int)s.momValid, (int)s.avValid, (int)s.dsValid,
-           (int)s.motionValid, (unsigned long long)s.epoch, extra.c_str());
+           (int)s.motionValid, (int)s.usValid, (unsigned long long)s.epoch, extra.c_str());
     fflush(stdout);
 }
 
