@@ -285,6 +285,12 @@ public:
     };
     void upsample(Pathtracer& lo, const UpsampleOptions& options);
     void upsample(Pathtracer& lo) { upsample(lo, UpsampleOptions()); }
+    // The same onto the planes of `planes`, a Pathtracer of the same scene and camera at exactly 2, 3 or 4 times this
+    // one's width and height that has had renderFeatures(camera): every pixel is the mean of the results at its S x S
+    // first-hit samples, so silhouettes are antialiased (pt_upsample_resolve, rule 9 of pt_hip.h).  This Pathtracer then
+    // needs neither features nor a render; nothing of `lo` or `planes` changes.
+    void upsample(Pathtracer& lo, Pathtracer& planes, const UpsampleOptions& options);
+    void upsample(Pathtracer& lo, Pathtracer& planes) { upsample(lo, planes, UpsampleOptions()); }
     void upsampleCounts(uint32_t counts[2]);
     bool upsampled() const;                          // an upsampled image made through this class is still held
     // Temporal reprojection (pt_temporal, pt_hip.h): per frame render(camera, spp, true), renderFeatures(camera),
@@ -428,6 +434,7 @@ struct Params {
     unsigned int m_minSpp = 0;       // CLI -minspp: samples every pixel gets (0 = two calls)
     bool m_despike = false;          // CLI -despike: the firefly clamp at its defaults before the image is written
     unsigned int m_upsample = 0;     // CLI -upsample K: trace at ceil(w / K) x ceil(h / K) and reconstruct the frame (0 = off)
+    unsigned int m_upsampleAa = 0;   // CLI -upsample_aa S: with -upsample, S x S first-hit samples per pixel (0 = one)
     unsigned int m_denoise = 0;      // CLI -denoise [N]: a-trous iterations applied before the image is written (0 = off)
     bool m_denoiseAdaptive = false;  // CLI -denoise_guide adaptive: the filter follows the adaptive render's own variance
 };

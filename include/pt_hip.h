@@ -996,6 +996,51 @@ PT_API int pt_upsample_image(int device, uint32_t lo_w, uint32_t lo_h, const flo
                              const float *hi_plane0, const float *hi_plane1, const float *hi_plane2,
                              const pt_upsample_params *params, float *out, uint32_t *out_counts);
 
+/* ---- Guided upsampling onto supersampled feature planes ---------------------------------------------
+ * Rule 8's high planes are one first-hit sample per pixel, so its result is stair-stepped along every silhouette.
+ * Rule 9 runs rule 8 onto the planes of an S-times larger frame of the same camera (S x S first-hit samples per
+ * output pixel, each jittered inside its own sub-pixel by pt_render_features) and gives every output pixel the mean
+ * of its S x S results; the S-times image is never written.  All float32, no contraction, + and / only beyond rule 8.
+ * tests/upsample_resolve_model.py restates it.
+ *
+ * 9. A low image and its planes at w x h (rule 8's), planes at S W x S H, a factor S in {2, 3, 4}, pt_upsample_params.
+ *    1 <= w <= W and 1 <= h <= H, and the S-times frame within rule 8's sizes (S W x S H < 2^30 pixels).
+ *    rule8(x, y) below is rule 8 with its W, H = S W, S H: sx = (float)w / (float)(S W), and so on.
+ *    The flat pass is rule 8's at the S-times size: F_q holds the S-times pixels whose nearest low pixel is q and that
+ *    carry its id, so D_q is a mean over up to S^2 K^2 albedo samples at a ratio of K.
+ *    Per output pixel (X, Y):
+ *     sum = (0, 0, 0)
+ *     for j = 0 .. S - 1 (outer), i = 0 .. S - 1 (inner):  sum = sum + rule8(S X + i, S Y + j).xyz      (per channel)
+ *     out.xyz = sum / (float)(S * S);   out.w = 1
+ *    The mean is of linear radiance, as an accumulation's is.  count_wide and count_nearest are rule 8's, summed over
+ *    all S W x S H sub-pixels.  A sub-pixel that is not finite makes its output pixel not finite (inf and -inf give
+ *    NaN); buffers compare as "words equal, or both NaN".
+ *    The staged rectangle: an output tile of 32 x 8 covers the S-times pixels S X0 .. S X0 + 32 S - 1, whose u differ
+ *    by (32 S - 1) * (w / (S W)) < 32 w / W <= 32; two reals less than 32 apart have floors at most 32 apart, so ring 1
+ *    reaches at most 32 + 2 = 34 columns and likewise 8 + 2 = 10 rows: within rule 8's 35 x 11 and the same LDS.  (In
+ *    float32 the coordinates of a frame wider than 2^24 are not exact; a rectangle that did not fit is read through
+ *    the caches, the same words.)
+ *    Two kernels: rule 8's flat pass, then upsample_resolve_kernel, one output pixel per lane on the 32 x 8 tile,
+ *    the lane walking its S x S sub-pixels in the rule's order; staging as rule 8. */
+/* Rule 9 from `lo`'s image and planes and `planes`' planes; the result is held by `hi` (hi's width x height float4) as
+ * its upsampled image: pt_holds_upsampled, pt_read_upsampled, pt_tonemap_upsampled, pt_read_upsample_counts and
+ * pt_read_upsample_timing (the flat pass, upsample_resolve_kernel) serve it as they serve pt_upsample's.  `hi` needs
+ * neither planes nor a render.  Refused, naming the reason: PT_ERR_ARG for a null argument, the parameters, an unknown
+ * source, contexts on different devices, a band partition on any of the three, a factor outside 2..4, a `planes` that
+ * is not exactly factor x `hi` in both dimensions, a `lo` larger than `hi` in either dimension; PT_ERR_STATE when the
+ * planes of `planes` or of `lo` are not current, or `lo` does not hold the source.  Errors are `hi`'s.  Nothing of any
+ * render state is written, nothing at all of `lo` or `planes` changes, and a refused call changes nothing. */
+PT_API int pt_upsample_resolve(pt_context *hi, pt_context *planes, pt_context *lo, uint32_t source, uint32_t frames,
+                               uint32_t factor, const pt_upsample_params *params);
+/* Rule 9 on host arrays, without a context: color and lo_plane0..2 are lo_h x lo_w float4, ss_plane0..2 are
+ * ss_h x ss_w float4 (the S-times planes), out is (ss_h / factor) x (ss_w / factor) float4, out_counts (optional)
+ * 2 x uint32.  PT_ERR_ARG also when factor does not divide ss_w and ss_h.  Errors: pt_last_error(NULL). */
+PT_API int pt_upsample_resolve_image(int device, uint32_t lo_w, uint32_t lo_h, const float *color, const float *lo_plane0,
+                                     const float *lo_plane1, const float *lo_plane2, uint32_t ss_w, uint32_t ss_h,
+                                     const float *ss_plane0, const float *ss_plane1, const float *ss_plane2,
+                                     uint32_t factor, const pt_upsample_params *params, float *out,
+                                     uint32_t *out_counts);
+
 /* ---- Moving objects in the temporal passes --------------------------------------------------------
  * Rule 3 (temporal reprojection) and rule 4's first part (the step with moments) project one world point with
  * two cameras: only the camera may move.  Rule 7 is the same step when the objects moved too: a per-primitive

@@ -159,6 +159,11 @@ PT_API int pth_renderer_despike_count(pth_renderer *r, uint32_t *count);
  * pth_renderer_upsample_counts: the pixels that needed the wider ring and those that took the nearest low pixel. */
 PT_API int pth_renderer_upsample(pth_renderer *hi, pth_renderer *lo, uint32_t source, const pt_upsample_params *params);
 PT_API int pth_renderer_upsample_counts(pth_renderer *r, uint32_t *counts);
+/* Pathtracer::upsample(lo, planes, options) (pt_upsample_resolve, rule 9 of pt_hip.h): the same onto the feature
+ * planes of `planes`, a renderer at exactly 2, 3 or 4 times hi's width and height, each pixel of `hi` the mean over
+ * its factor x factor first-hit samples.  `hi` needs neither features nor a render. */
+PT_API int pth_renderer_upsample_resolve(pth_renderer *hi, pth_renderer *planes, pth_renderer *lo, uint32_t source,
+                                         const pt_upsample_params *params);
 PT_API float pth_renderer_timing(const pth_renderer *r);
 PT_API uint32_t pth_renderer_frames(const pth_renderer *r);
 PT_API uint32_t pth_renderer_local_rows(const pth_renderer *r);

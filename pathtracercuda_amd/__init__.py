@@ -31,7 +31,7 @@ __all__ = ["Pathtracer", "Scene", "make_camera", "camera_rotate", "camera_transl
            "temporal_moments_image", "denoise_variance_image", "VARIANCE_DEFAULTS", "VDENOISE_DEFAULTS",
            "vfeedback_params", "denoise_variance_feedback_image", "VFEEDBACK_DEFAULTS", "adaptive_variance_params",
            "adaptive_variance_image", "AVARIANCE_DEFAULTS", "ADENOISE_SIGMA_L", "despike_params", "despike_image",
-           "DESPIKE_DEFAULTS", "upsample_params", "upsample_image", "UPSAMPLE_DEFAULTS", "UPSAMPLE_SOURCES", "motion_table", "temporal_motion_image", "temporal_moments_motion_image", "NO_PREVIOUS"]
+           "DESPIKE_DEFAULTS", "upsample_params", "upsample_image", "upsample_resolve_image", "UPSAMPLE_DEFAULTS", "UPSAMPLE_SOURCES", "motion_table", "temporal_motion_image", "temporal_moments_motion_image", "NO_PREVIOUS"]
 
 HITTABLE_TYPES = ["SPHERE", "CYLINDER", "DISK", "CONE", "PARABOLOID", "QUAD", "CUBE"]   # Hittable.h:9-12
 MATERIAL_TYPES = ["LAMBERT", "GGX", "LAMBERT_GGX"]                                     # Material.h:9-12
@@ -669,6 +669,39 @@ def upsample_image(color, lo_plane0, lo_plane1, lo_plane2, hi_plane0, hi_plane1,
     return (out, (int(counts[0]), int(counts[1]))) if return_counts else out
 
 
+def upsample_resolve_image(color, lo_plane0, lo_plane1, lo_plane2, ss_plane0, ss_plane1, ss_plane2, factor: int,
+                           sigma_plane: Optional[float] = None, normal_power_log2: Optional[int] = None,
+                           demodulate: Optional[bool] = None, same_primitive: Optional[bool] = None, staging: int = 0,
+                           device: int = 0, return_counts: bool = False):
+    """pt_upsample_resolve_image: the guided upsampling onto supersampled planes (rule 9 of include/pt_hip.h) on host
+    arrays, without a Pathtracer: the colour and the three feature planes of a low image (h x w x 4 float32) and the
+    three planes of a frame `factor` (2, 3 or 4) times the output in width and height (S H x S W x 4, w <= W and
+    h <= H).  Returns H x W x 4, every pixel the mean of rule 8's result at its S x S samples, or (image, (sub-pixels
+    that needed the wider ring, sub-pixels that took the nearest low pixel)) with return_counts."""
+    params = upsample_params(sigma_plane, normal_power_log2, demodulate, same_primitive, staging)
+    if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)) or not 2 <= int(factor) <= 4:
+        raise _refuse(f"upsample_resolve_image: factor must be 2, 3 or 4, not {factor!r}")
+    S = int(factor)
+    c = _image4("color", color)
+    lows = [_image4(f"lo_plane{k}", p, c.shape) for k, p in enumerate((lo_plane0, lo_plane1, lo_plane2))]
+    h0 = _image4("ss_plane0", ss_plane0)
+    highs = [h0] + [_image4(f"ss_plane{k + 1}", p, h0.shape) for k, p in enumerate((ss_plane1, ss_plane2))]
+    if h0.shape[0] % S or h0.shape[1] % S:
+        raise _refuse(f"upsample_resolve_image: factor {S} does not divide the planes {h0.shape[:2]}")
+    H, W = h0.shape[0] // S, h0.shape[1] // S
+    if c.shape[0] > H or c.shape[1] > W:
+        raise _refuse(f"upsample_resolve_image: the low image {c.shape[:2]} is larger than the output {(H, W)}")
+    out = np.zeros((H, W, 4), dtype=np.float32)
+    counts = (C.c_uint32 * 2)()
+    fp = C.POINTER(C.c_float)
+    rc = N.hip().pt_upsample_resolve_image(int(device), c.shape[1], c.shape[0], c.ctypes.data_as(fp),
+                                           *[p.ctypes.data_as(fp) for p in lows], h0.shape[1], h0.shape[0],
+                                           *[p.ctypes.data_as(fp) for p in highs], S, C.byref(params),
+                                           out.ctypes.data_as(fp), counts)
+    N.check_ctx(rc, None)
+    return (out, (int(counts[0]), int(counts[1]))) if return_counts else out
+
+
 class Scene:
     """A parsed scene file (no GPU): objects in file order, the SAH BVH, camera, textures."""
 
@@ -1078,12 +1111,16 @@ class Pathtracer:
     # --- guided upsampling of a low-resolution render (pt_upsample; rule 8 of pt_hip.h) ----------------
     def upsample(self, lo: "Pathtracer", source: str = "accum", frames: Optional[int] = None,
                  sigma_plane: Optional[float] = None, normal_power_log2: Optional[int] = None,
-                 demodulate: Optional[bool] = None, same_primitive: Optional[bool] = None, staging: int = 0) -> np.ndarray:
+                 demodulate: Optional[bool] = None, same_primitive: Optional[bool] = None, staging: int = 0,
+                 planes: Optional["Pathtracer"] = None) -> np.ndarray:
         """Reconstruct this Pathtracer's frame from the image of `lo`, a Pathtracer of the same scene and camera at a
         lower resolution (include/pt_hip.h, rule 8): every pixel takes the demodulated colour of the low pixels around
         it that lie on its surface, times its own albedo.  Both need the planes of a features(camera) call; this one
         needs no render.  source: "accum" (lo's render, over `frames`, default lo.frames), "denoised", "temporal" or
         "despiked" (what lo holds).  Returns rows x width x 4 float32 and leaves both render states as they are.
+        planes: a Pathtracer of the same scene and camera at exactly 2, 3 or 4 times this one's width and height that
+        has had features(camera); every pixel is then the mean of the result at its S x S first-hit samples, which
+        antialiases the silhouettes (rule 9, pt_upsample_resolve), and this Pathtracer needs no features of its own.
         Arguments out of range raise before any device call."""
         self._single("upsample")
         params = upsample_params(sigma_plane, normal_power_log2, demodulate, same_primitive, staging)
@@ -1097,6 +1134,14 @@ class Pathtracer:
         f = lo.frames if frames is None else int(frames)
         if not 0 <= f <= 0xffffffff:
             raise _refuse(f"upsample: frames must be 0..2^32 - 1, not {frames!r}")
+        if planes is not None:
+            if not isinstance(planes, Pathtracer):
+                raise _refuse(f"upsample: planes must be a Pathtracer, not {type(planes).__name__}")
+            planes._single("upsample")
+            factor = planes.width // self.width       # (anything but exactly 2..4 times this frame is refused by name)
+            N.check_ctx(N.hip().pt_upsample_resolve(self._ctx, planes._ctx, lo._ctx, UPSAMPLE_SOURCES[source], f, factor,
+                                                    C.byref(params)), self._ctx)
+            return self.upsampled()
         N.check_ctx(N.hip().pt_upsample(self._ctx, lo._ctx, UPSAMPLE_SOURCES[source], f, C.byref(params)), self._ctx)
         return self.upsampled()
 
@@ -1116,7 +1161,8 @@ class Pathtracer:
 
     def upsample_counts(self) -> Dict[str, int]:
         """Of the last upsample(): {"wide": guided pixels that needed the second ring, "nearest": guided pixels no tap
-        of either ring served, which took the nearest low pixel} (pt_read_upsample_counts)."""
+        of either ring served, which took the nearest low pixel} (pt_read_upsample_counts).  After upsample(lo,
+        planes=...) both count first-hit samples, up to S * S per pixel."""
         self._single("upsample_counts")
         n = (C.c_uint32 * 2)()
         N.check_ctx(N.hip().pt_read_upsample_counts(self._ctx, n), self._ctx)

@@ -221,6 +221,10 @@ _HIP_SYMBOLS = {
     "pt_read_upsample_timing": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "pt_upsample_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 4 + [C.c_uint32, C.c_uint32]
                           + [P(C.c_float)] * 3 + [P(PtUpsampleParams), P(C.c_float), P(C.c_uint32)]),
+    "pt_upsample_resolve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      P(PtUpsampleParams)]),
+    "pt_upsample_resolve_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 4 + [C.c_uint32, C.c_uint32]
+                                  + [P(C.c_float)] * 3 + [C.c_uint32, P(PtUpsampleParams), P(C.c_float), P(C.c_uint32)]),
     "pt_set_scene_moved": (C.c_int, [C.c_void_p, P(PtBvhNode), C.c_uint32, P(PtHittable), C.c_uint32, P(C.c_float),
                                      P(C.c_uint32)]),
     "pt_holds_motion": (C.c_int, [C.c_void_p]),
@@ -293,6 +297,7 @@ _HOST_SYMBOLS = {
     "pth_renderer_despike": (C.c_int, [C.c_void_p, P(PtDespikeParams)]),
     "pth_renderer_despike_count": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
     "pth_renderer_upsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, P(PtUpsampleParams)]),
+    "pth_renderer_upsample_resolve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, P(PtUpsampleParams)]),
     "pth_renderer_upsample_counts": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
     "pth_renderer_timing": (C.c_float, [C.c_void_p]),
     "pth_renderer_frames": (C.c_uint32, [C.c_void_p]),

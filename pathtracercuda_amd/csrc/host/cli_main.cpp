@@ -24,6 +24,9 @@
 //   -upsample K    K = 2..4: trace (and -despike / -denoise) at ceil(w / K) x ceil(h / K), take the first-hit features at
 //                  both sizes and reconstruct the w x h image from them (Pathtracer::upsample, rule 8 of pt_hip.h).
 //                  One GPU; not with -denoise_guide adaptive.
+//   -upsample_aa S S = 2..4, with -upsample K only: take the full-size features at S w x S h, S x S first-hit samples
+//                  per pixel, and give every pixel the mean of the reconstruction at its samples, which antialiases
+//                  the silhouettes (Pathtracer::upsample(lo, planes), rule 9 of pt_hip.h).
 // The windowed / interactive mode (-window, -enable_controls) is not supported.
 #include <algorithm>
 #include <cstdio>
@@ -121,6 +124,16 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
             i += 2;
             continue;
         }
+        if (strcmp(argv[i], "-upsample_aa") == 0) {
+            char* end = nullptr;
+            const long s = i + 1 < argc ? strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || s < 2 || s > 4) {
+                printf("Invalid input for -upsample_aa! (a factor of 2..4)\n");
+                displayHelp = true;
+            } else params.m_upsampleAa = (unsigned int)s;
+            i += 2;
+            continue;
+        }
         if (strcmp(argv[i], "-minspp") == 0) { uintArg(i, "-minspp", params.m_minSpp); i += 2; continue; }
         printf("Can't parse argument: %s\n", argv[i]);
         displayHelp = true;
@@ -136,6 +149,10 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
     }
     if (params.m_upsample && params.m_denoiseAdaptive) {
         printf("Invalid input for -upsample! (not with -denoise_guide adaptive)\n");
+        displayHelp = true;
+    }
+    if (params.m_upsampleAa && !params.m_upsample) {
+        printf("Invalid input for -upsample_aa! (needs -upsample K)\n");
         displayHelp = true;
     }
     // (`pathtracer -help` alone lists the options: the lone argument is not an input file)
@@ -169,6 +186,8 @@ static bool processArgs(int argc, char* argv[], Params& params, int& gpus)
         printf("%-30s Clamp fireflies before writing (and before -denoise): same-surface neighbourhood limit\n", "-despike");
         printf("%-30s Trace at 1/K of the width and height, K = 2..4, and reconstruct the image from full-size features\n",
                "-upsample K");
+        printf("%-30s With -upsample: antialias the reconstruction with S x S first-hit samples per pixel, S = 2..4\n",
+               "-upsample_aa S");
         return false;
     }
     params.m_enableControls = params.m_enableControls && params.m_showWindow;
@@ -289,12 +308,23 @@ int main(int argc, char* argv[])
 
     if (K) {
         if (!params.m_despike && !params.m_denoise) pathtracer->renderFeatures(camera);
-        full->renderFeatures(camera);
-        full->upsample(*pathtracer);
+        const uint32_t S = params.m_upsampleAa;
+        if (S) {          // the planes of an S-times frame of the same camera; `full` then takes no features of its own
+            Pathtracer super(params.m_width * S, params.m_height * S);
+            loadScene(super, params);
+            super.renderFeatures(camera);
+            full->upsample(*pathtracer, super);
+        } else {
+            full->renderFeatures(camera);
+            full->upsample(*pathtracer);
+        }
         uint32_t counts[2] = {0, 0};
         full->upsampleCounts(counts);
-        printf("Upsampled: %u x %u from %u x %u, %u pixels from the wider ring, %u from the nearest pixel\n", params.m_width,
-               params.m_height, (params.m_width + K - 1) / K, (params.m_height + K - 1) / K, counts[0], counts[1]);
+        if (S) printf("Antialiased: %u x %u first-hit samples per pixel\n", S, S);
+        // (with -upsample_aa the counts are of first-hit samples, up to S * S per pixel)
+        printf(S ? "Upsampled: %u x %u from %u x %u, %u samples from the wider ring, %u from the nearest pixel\n"
+                 : "Upsampled: %u x %u from %u x %u, %u pixels from the wider ring, %u from the nearest pixel\n",
+               params.m_width, params.m_height, (params.m_width + K - 1) / K, (params.m_height + K - 1) / K, counts[0], counts[1]);
         pathtracer = std::move(full);
     }
 

@@ -534,6 +534,23 @@ PT_API int pth_renderer_upsample(pth_renderer* hi, pth_renderer* lo, uint32_t so
     PTH_GUARD_END
 }
 
+PT_API int pth_renderer_upsample_resolve(pth_renderer* hi, pth_renderer* planes, pth_renderer* lo, uint32_t source,
+                                         const pt_upsample_params* params)
+{
+    if (!hi || !planes || !lo || !params) return setError(PT_ERR_ARG, "invalid argument");
+    pth_renderer* r = hi;
+    PTH_GUARD_BEGIN
+    Pathtracer::UpsampleOptions o;
+    o.source = source;
+    o.sigmaPlane = params->sigma_plane;
+    o.normalPowerLog2 = params->normal_power_log2;
+    o.flags = params->flags;
+    o.staging = params->staging;
+    r->pt->upsample(*lo->pt, *planes->pt, o);
+    return PT_OK;
+    PTH_GUARD_END
+}
+
 PT_API int pth_renderer_upsample_counts(pth_renderer* r, uint32_t* counts)
 {
     if (!r || !counts) return setError(PT_ERR_ARG, "invalid argument");

@@ -358,6 +358,18 @@ void Pathtracer::upsample(Pathtracer& lo, const UpsampleOptions& o)
     m_upsampled = true;
 }
 
+void Pathtracer::upsample(Pathtracer& lo, Pathtracer& planes, const UpsampleOptions& o)
+{
+    if (m_group || lo.m_group || planes.m_group) check(PT_ERR_STATE, "upsample: not available on a device group");
+    uint32_t source = o.source;
+    if (source == kUpsampleAuto)
+        source = lo.m_denoised ? PT_UPSAMPLE_DENOISED : (lo.despiked() ? PT_UPSAMPLE_DESPIKED : PT_UPSAMPLE_ACCUM);
+    const pt_upsample_params p = {o.sigmaPlane, o.normalPowerLog2, o.flags, o.staging};
+    const uint32_t factor = planes.m_width / m_width;         // (anything but exactly 2..4 times this frame is refused below)
+    check(pt_upsample_resolve(m_ctx, planes.m_ctx, lo.m_ctx, source, lo.m_accumulatedFrames, factor, &p), "pt_upsample_resolve");
+    m_upsampled = true;
+}
+
 // (as despiked(): the class's flag and the context's fact)
 bool Pathtracer::upsampled() const { return m_upsampled && !m_group && pt_holds_upsampled(m_ctx) != 0; }
 

@@ -117,6 +117,9 @@ PT_DEV void us_tap(const UpsampleArgs& A, float b, bool inside, const float4 Np,
 // tile's last pixel again and stores and counts nothing.
 // The two counts: one ballot per wave, summed over the workgroup's four waves in LDS, then at most one atomic add
 // each; integer adds commute, so the counts are the same in any order.
+// The per-pixel body below (from the loads of Ap, Np, Pp to the nearest-pixel fallback) has a second copy,
+// us_resolve_pixel in pt_dev_upsample_resolve.h, which must stay operation for operation the same: a change to one
+// needs the other.  tests/test_gpu_upsample_resolve.py holds them together (the box mean of this kernel's image).
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t kUsMaxRN = (kDnTileW + 3u) * (kDnTileH + 3u);
 constexpr uint32_t kUsCountF4 = 2u;             // 8 words ahead of the staged texels: 4 waves x 2 counts

@@ -455,6 +455,8 @@ __global__ void __launch_bounds__(256) adapt_scatter_kernel(const unsigned long 
 
 #include "pt_dev_upsample.h"
 
+#include "pt_dev_upsample_resolve.h"
+
 // Multi-device gather, second half: scatter one device's received rows (its bands, in local row
 // order) into the full image.  A band is band-rows consecutive image rows in both buffers, so every
 // lane copies one float4 of a coalesced row.
@@ -2086,6 +2088,8 @@ PT_API int pt_set_kernel_variant(pt_context* ctx, int variant)
 #include "pt_despike.h"
 
 #include "pt_upsample.h"
+
+#include "pt_upsample_resolve.h"
 
 extern "C" PT_API const char* pt_last_error(const pt_context* ctx)
 {

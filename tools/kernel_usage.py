@@ -10,6 +10,7 @@ With --against: every kernel of the old report must have identical figures in th
 the kernels only the new report has are listed with their figures.
 """
 import argparse
+import hashlib
 import json
 import re
 import subprocess
@@ -30,6 +31,12 @@ def parse(path):
     return out
 
 
+def table_hash(table):
+    """sha256 of the whole table (mangled name -> figures, keys sorted): a build of the same tree prints the same one
+    (`python tools/kernel_usage.py report.txt` shows it as table_sha256), so a recorded comparison can be re-checked."""
+    return hashlib.sha256(json.dumps(table, sort_keys=True).encode()).hexdigest()
+
+
 def demangle(names):
     try:
         r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True)
@@ -43,16 +50,19 @@ def main():
     ap.add_argument("report")
     ap.add_argument("--against")
     ap.add_argument("--out")
+    ap.add_argument("--against-label", help="what the --against report is of (a commit id and how it was made)")
     a = ap.parse_args()
     new = parse(a.report)
-    record = {"kernels": len(new)}
+    record = {"kernels": len(new), "table_sha256": table_hash(new)}
     rc = 0
     if a.against:
         old = parse(a.against)
         changed = sorted(k for k in old if old[k] != new.get(k))
         added = sorted(k for k in new if k not in old)
         names = demangle(added + changed)
-        record.update(parent_kernels=len(old), parent_trace_kernel_instantiations=sum("trace_kernel" in k for k in old),
+        if a.against_label:
+            record["parent_report"] = a.against_label
+        record.update(parent_kernels=len(old), parent_table_sha256=table_hash(old), parent_trace_kernel_instantiations=sum("trace_kernel" in k for k in old),
                       parent_kernels_with_other_figures=[names[k] for k in changed],
                       new_kernels={names[k]: new[k] for k in added})
         rc = 1 if changed else 0
