@@ -134,8 +134,13 @@ public:
     HittableType type() const { return m_type; }
     const float* invTransformRows() const { return &m_invTransformRows[0][0]; }
     const Material& material() const { return m_material; }
+    // what the constructor was given (rotation in radians); the default object: the origin, no rotation, scale 1
+    const vec3& position() const { return m_position; }
+    const vec3& rotation() const { return m_rotation; }
+    const vec3& scale() const { return m_scale; }
 
 private:
+    vec3 m_position = vec3(0.0f), m_rotation = vec3(0.0f), m_scale = vec3(1.0f);
     float m_invTransformRows[3][4];
     Material m_material;
     AABB m_aabb;
@@ -158,6 +163,9 @@ public:
     const std::vector<CpuHittable>& getElements() const { return m_elements; }
     uint32_t getDepth(uint32_t node = 0) const;
     bool validate();
+    // Elements elementIndex[k] replaced by elements[k] and every node's box refitted (rule 10 of pt_hip.h,
+    // ptamd::refitBoxes): the topology stays.  What Pathtracer::moveObjects does to its mirror of the device's tree.
+    void refit(size_t count, const uint32_t* elementIndex, const CpuHittable* elements);
 
 private:
     uint32_t m_maxLeafElements = 1;
@@ -204,6 +212,21 @@ public:
     // setScene.  One move per temporal step: a second move before the next temporal() ends the history.  Objects
     // that are word for word the same are told apart by their order in the array.  Single device only.
     void setSceneMoved(size_t count, const CpuHittable* hittables, const uint32_t* previousObject = nullptr);
+    // Move objects without a rebuild (pt_move_primitives, rule 10 of pt_hip.h): object[k], an index into the last
+    // scene's array, becomes hittables[k].  An upload of the moved objects' records and a refit of the existing tree on
+    // the device (only the upload scales with what moved: the refit, here and on the device, and the motion table run over
+    // the whole scene); the temporal history is kept exactly as setSceneMoved keeps it (the motion rows come from the two
+    // transforms; one move per temporal step), and motionRows / motionPrevIndex answer as after setSceneMoved.  The
+    // tree is afterwards no longer the one BVH::build would make for the new poses: renders equal the oracle walking
+    // bvh(), which this class keeps equal to the device's tree; rebuildScene() returns to the build's tree.  Refused,
+    // with nothing of this class or the device changed: a device group, no scene, count 0, a null array, an index
+    // out of range or given twice, whatever pt_move_primitives refuses.
+    void moveObjects(size_t count, const uint32_t* object, const CpuHittable* hittables);
+    // setSceneMoved of the current objects onto themselves: a fresh SAH tree, the history kept.  For when a refitted
+    // tree has grown slow.
+    void rebuildScene();
+    const std::vector<CpuHittable>& sceneObjects() const { return m_sceneObjects; }
+    float refitTiming();                             // pt_read_refit_timing of the last moveObjects, ms
     bool holdsMotion() const;                        // a motion table is held for the next temporal step
     const std::vector<float>& motionRows() const { return m_motionRows; }
     const std::vector<uint32_t>& motionPrevIndex() const { return m_motionPrev; }
@@ -471,6 +494,12 @@ float radians(float degree);   // SceneLoader.cpp:193-196
 // to float32 (the operation order is written out at pth_motion_table, pt_host.h).  False when a word of T is not
 // finite.
 bool motionRows(const float* prevInvRows, const float* curInvRows, float* out);
+
+// Rule 10 of pt_hip.h on the host: the boxes of every node reachable from the root refitted in place from one box per
+// primitive (primCount x 6 floats: min xyz, max xyz); offsets, counts and unreachable nodes keep their words.  False,
+// with `error` set and nothing changed, when the nodes are not a tree over the primitives or a box is not finite or
+// not ordered.
+bool refitBoxes(pt_bvh_node* nodes, uint32_t nodeCount, const float* boxes, uint32_t primCount, std::string& error);
 
 // Image I/O (stb_image / stb_image_write semantics for the formats the project uses).
 bool isHdrFile(const std::string& path);

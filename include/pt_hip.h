@@ -1110,6 +1110,79 @@ PT_API int pt_temporal_moments_motion_image(int device, uint32_t width, uint32_t
                                             float *out_hist3, float *out_variance, uint32_t prim_count,
                                             const float *motion_rows, const uint32_t *prev_index);
 
+/* ---- Moving primitives without a rebuild: the refit -------------------------------------------------
+ * pt_set_scene_moved replaces the whole scene: a new tree, four arrays freed, allocated and uploaded.  When the
+ * objects only moved, the topology -- which node is whose child, which primitives a leaf holds, the leaf words of the
+ * child-box records, the LDS stack rows, dfsOrder -- depends on no box value, and the tree can be REFITTED: the
+ * moved primitives' records replaced, and the boxes of the nodes recomputed from the leaves up.  Rule 10 says what a
+ * refit computes.  Compares and selects only, so the result is a function of (topology, boxes) alone;
+ * tests/refit_model.py restates it.
+ *
+ * 10. The refit.  Inputs: the tree's topology as pt_set_scene accepted it; one box per primitive i,
+ *     B_i = (min[3], max[3]), every word finite and min[k] <= max[k].  For every node reachable from the root:
+ *      a leaf with first primitive f and count c:
+ *        lo = B_f.min, hi = B_f.max;  then for k = 1 .. c - 1 in index order, with B = B_(f+k), per axis
+ *        lo = B.min < lo ? B.min : lo,   hi = B.max > hi ? B.max : hi
+ *      an interior node i with children a = i + 1 and b = offset, both done before it:  per axis
+ *        lo = b.lo < a.lo ? b.lo : a.lo,   hi = b.hi > a.hi ? b.hi : a.hi
+ *     Words written: the node's box takes (lo, hi); offset and primitive_count_axis keep their words.  Where the
+ *     context holds child-box records, an interior node's record takes its children's new boxes; its fourth quad
+ *     (the child words, the axis bit, the second child's first primitive) keeps its words.  A node that is not
+ *     reachable from the root, and its record, keep every word.
+ *     With the boxes a host build folded its nodes from, the refit reproduces that build's node boxes as float
+ *     values; only the sign of a zero can differ, because the order of the fold differs.
+ *     After a refit the tree is no longer the one a fresh build would make for the new poses: it is a valid tree over
+ *     them, usually a slower one, and a render equals the oracle walking that same tree (the contract a caller's own
+ *     BVH has always had: tie order and the rising-t_max rule depend on the tree).  A fresh pt_set_scene[_moved]
+ *     returns to the build's tree.
+ *     Kernels: motion_fill_kernel, move_scatter_kernel, refit_leaves_kernel, and refit_level_kernel launched once per
+ *     depth of interior nodes, the deepest first (at most 32 launches).  Nothing waits inside a launch.
+ *
+ * Not covered: device groups (refused by name); adding or removing primitives or changing the topology (use
+ * pt_set_scene_moved); two moves in one temporal step (the second ends the history, as with pt_set_scene_moved). */
+/* The boxes of the current scene's primitives, prim_count x 6 floats (min xyz, max xyz), which pt_set_scene's
+ * arguments do not carry: uploads them, reads the node topology back from the device once and keeps the lists of
+ * reachable leaves and of reachable interior nodes by depth.  Nothing of the scene changes and no fact but "the boxes
+ * are held" moves.  PT_ERR_ARG naming the primitive and the component for a word that is not finite or a min above
+ * its max; PT_ERR_STATE without a scene, or on a context of a device group.  Held until the next pt_set_scene,
+ * pt_set_scene_moved or pt_set_texture (a texture touches no box; ending the boxes there spares a second event and
+ * costs one more call of this function). */
+PT_API int pt_set_primitive_boxes(pt_context *ctx, const float *boxes);
+/* 1 while the boxes are held, else 0 (a question, never an error). */
+PT_API int pt_holds_primitive_boxes(const pt_context *ctx);
+/* Move `count` primitives in place and refit the tree (rule 10).  index: distinct primitive indices of the scene (its
+ * element order, as pt_set_scene took them); prims: their whole new records, checked as pt_set_scene checks a
+ * primitive; boxes: count x 6, their new boxes, checked as above.
+ * With motion_rows (count x 12) and prev_index (count; each its own index[j] or 0xffffffff): rule 7's table is made
+ * on the device -- the identity and prev_index = i for every primitive not named, the given entry for the named ones
+ * -- and the call raises what pt_set_scene_moved raises: over a held history the history, its moments and the table
+ * are held for the next temporal pass; a second move before that pass ends all three.  Without them (both null) the
+ * call is a scene change as pt_set_scene is.  Either way the feature planes end, and the boxes stay held.
+ * Refused, naming the reason, with no word on the device changed and no event raised: PT_ERR_ARG for a null index,
+ * prims or boxes, one of motion_rows and prev_index without the other, count == 0, an index given twice or not below
+ * the primitive count, a primitive, box or prev_index that fails its check; PT_ERR_STATE when no boxes are held or
+ * the context is part of a device group.
+ * One packed host-to-device copy of 208 bytes per moved primitive, then kernels on the context's stream; the root's
+ * new box is read back (32 bytes) for the trace kernel's by-value parameter, so the call returns with the work done.
+ * A move that fails midway (a HIP error, PT_ERR_HIP) may have written part of its words.  With motion rows it then
+ * raises a scene change: no history, no table, and the boxes not held.  Without them it already was a scene change;
+ * the boxes stay held (the lists are of the topology, which no move touches).  Either way set the scene again.
+ * Only the copy scales with `count`: the table's fill runs over every primitive and the refit over every reachable node.
+ * The fast slab test stays chosen as pt_set_scene chose it (a tree that had an unordered reachable box keeps the exact
+ * one after a refit has ordered its boxes; the words rendered are the same). */
+PT_API int pt_move_primitives(pt_context *ctx, uint32_t count, const uint32_t *index, const pt_hittable *prims,
+                              const float *boxes, const float *motion_rows, const uint32_t *prev_index);
+/* What the device holds, for tests and diagnosis.  pt_read_bvh: the node_count nodes in pt_bvh_node's layout, and,
+ * when records is not null and the context holds child-box records, max(interior nodes, 1) x 16 floats of them (a
+ * context without records leaves the array as it was).  pt_read_primitive: dst[0..15] the primitive's four quads,
+ * dst[16..27] its material's three. */
+PT_API int pt_read_bvh(pt_context *ctx, pt_bvh_node *nodes, float *records);
+PT_API int pt_read_primitive(pt_context *ctx, uint32_t index, float *dst);
+/* Three floats about the last pt_move_primitives: dst[0] = hipEvent milliseconds of its kernels (the fill, the scatter,
+ * the leaves, the levels); dst[1] = host milliseconds of the packing; dst[2] = hipEvent milliseconds of the one
+ * host-to-device copy.  PT_ERR_STATE before the first move. */
+PT_API int pt_read_refit_timing(pt_context *ctx, float *dst);
+
 /* ---- Multi-device group (one process, one context per GPU, RCCL over xGMI) -------------------
  * Replaces the reference's hard-coded single device (Pathtracer.cpp:40: cudaSetDevice(0)) behind
  * the same Pathtracer interface: device i renders the row bands b = i, i + N, ... of the image

@@ -85,6 +85,29 @@ PT_API int pth_renderer_load_scene_moved(pth_renderer *r, const char *path, cons
                                          pt_camera *camera);
 PT_API int pth_renderer_holds_motion(const pth_renderer *r);
 PT_API uint32_t pth_renderer_motion_table(const pth_renderer *r, const float **rows, const uint32_t **prev_index);
+/* Moving objects without a rebuild (Pathtracer::moveObjects; pt_move_primitives and rule 10 of pt_hip.h).  object:
+ * `count` distinct indices into the last scene's objects (the file's order); position, rotation (radians, as the
+ * CpuHittable constructor takes it) and scale: count x 3 floats, the objects' new transforms.  Type and material stay
+ * what the object has.  The temporal history is kept as pth_renderer_load_scene_moved keeps it, and
+ * pth_renderer_motion_table answers as after it.  Refused with nothing changed: a device group or no scene
+ * (PT_ERR_STATE), count 0, a null array, an index out of range or given twice, a transform whose inverse is not finite
+ * (PT_ERR_ARG). */
+PT_API int pth_renderer_move_objects(pth_renderer *r, uint32_t count, const uint32_t *object, const float *position,
+                                     const float *rotation, const float *scale);
+/* Pathtracer::rebuildScene: a fresh SAH build of the current objects, the history kept (a move onto themselves). */
+PT_API int pth_renderer_rebuild_scene(pth_renderer *r);
+/* The transforms the current objects were made with, count x 3 floats each (null arrays are skipped); returns the
+ * number of objects. */
+PT_API uint32_t pth_renderer_object_transforms(const pth_renderer *r, float *position, float *rotation, float *scale);
+/* hipEvent milliseconds of the last move's kernels (pt_read_refit_timing). */
+PT_API int pth_renderer_refit_timing(pth_renderer *r, float *ms);
+/* The tree this renderer holds, which mirrors the device's: after pth_renderer_move_objects the refitted one.  The
+ * counts are always written; null arrays are skipped. */
+PT_API int pth_renderer_bvh(const pth_renderer *r, pt_bvh_node *nodes, pt_hittable *prims, uint32_t *node_count,
+                            uint32_t *prim_count);
+/* Rule 10 of pt_hip.h on the host, in place (ptamd::refitBoxes): boxes = prim_count x 6 floats.  PT_ERR_ARG, with
+ * nothing changed, when the nodes are no tree over the primitives or a box is not finite or not ordered.  Pure CPU. */
+PT_API int pth_refit_boxes(pt_bvh_node *nodes, uint32_t node_count, const float *boxes, uint32_t prim_count);
 /* Rule 7's map for `count` objects from their records in two scenes; pure CPU, no HIP call.  With the world->object
  * rows [A | b] of prev[i] and cur[i] (inv_transform_rows), T_i = [inverse(A_prev) A_cur | inverse(A_prev) (b_cur -
  * b_prev)] takes a world point on the object now to where that object point was.  Computed in float64 from the

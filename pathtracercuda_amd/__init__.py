@@ -31,7 +31,7 @@ __all__ = ["Pathtracer", "Scene", "make_camera", "camera_rotate", "camera_transl
            "temporal_moments_image", "denoise_variance_image", "VARIANCE_DEFAULTS", "VDENOISE_DEFAULTS",
            "vfeedback_params", "denoise_variance_feedback_image", "VFEEDBACK_DEFAULTS", "adaptive_variance_params",
            "adaptive_variance_image", "AVARIANCE_DEFAULTS", "ADENOISE_SIGMA_L", "despike_params", "despike_image",
-           "DESPIKE_DEFAULTS", "upsample_params", "upsample_image", "upsample_resolve_image", "UPSAMPLE_DEFAULTS", "UPSAMPLE_SOURCES", "motion_table", "temporal_motion_image", "temporal_moments_motion_image", "NO_PREVIOUS"]
+           "DESPIKE_DEFAULTS", "upsample_params", "upsample_image", "upsample_resolve_image", "UPSAMPLE_DEFAULTS", "UPSAMPLE_SOURCES", "motion_table", "refit_boxes", "temporal_motion_image", "temporal_moments_motion_image", "NO_PREVIOUS"]
 
 HITTABLE_TYPES = ["SPHERE", "CYLINDER", "DISK", "CONE", "PARABOLOID", "QUAD", "CUBE"]   # Hittable.h:9-12
 MATERIAL_TYPES = ["LAMBERT", "GGX", "LAMBERT_GGX"]                                     # Material.h:9-12
@@ -251,6 +251,21 @@ def motion_table(prev_objects, cur_objects):
                                                rows.ctypes.data_as(C.POINTER(C.c_float)),
                                                valid.ctypes.data_as(C.POINTER(C.c_uint32))))
     return rows, valid != 0
+
+
+def refit_boxes(nodes, boxes):
+    """pth_refit_boxes: rule 10 of include/pt_hip.h on the host.  nodes: a sequence of PtBvhNode (or a ctypes array of
+    them); boxes: prim_count x 6 float32 (min xyz, max xyz).  Returns a new PtBvhNode array: every node reachable from
+    the root with its box refitted, every other word as it was.  Pure CPU."""
+    src = list(nodes)
+    if not src:
+        raise _refuse("refit_boxes: nodes is empty")
+    b = np.ascontiguousarray(boxes, dtype=np.float32)
+    if b.ndim != 2 or b.shape[1] != 6 or b.shape[0] == 0:
+        raise _refuse(f"refit_boxes: boxes must be prim_count x 6, not {b.shape}")
+    out = (PtBvhNode * len(src))(*[PtBvhNode.from_buffer_copy(n) for n in src])
+    N.check_host(N.host().pth_refit_boxes(out, len(src), b.ctypes.data_as(C.POINTER(C.c_float)), b.shape[0]))
+    return out
 
 
 def _motion_arrays(what: str, motion_rows, prev_index):
@@ -861,6 +876,62 @@ class Pathtracer:
             self._r, os.fsencode(str(path)), prev.ctypes.data_as(C.POINTER(C.c_uint32)) if prev is not None else None,
             C.byref(cam)))
         return cam
+
+    def move_objects(self, indices, position, rotation, scale) -> None:
+        """Move objects without a rebuild (pth_renderer_move_objects; pt_move_primitives, rule 10 of include/pt_hip.h).
+        indices: n distinct object indices in the scene file's order; position, rotation (radians), scale: n x 3, the
+        new transforms (type and material stay).  An upload of the n records and a refit of the existing tree on the
+        device (only the upload scales with n: the refit and the motion table run over the whole scene); the temporal history is kept as load_scene_moved keeps it.  Per frame: move_objects(...),
+        render(cam, 1, True), features(cam), temporal(...).  The tree is afterwards not the one a fresh build would
+        make: renders equal the oracle walking bvh(); rebuild_scene() returns to the build's tree.  Single device
+        only."""
+        self._single("move_objects")
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        if idx.size == 0:
+            raise _refuse("move_objects: indices is empty")
+        if (idx < 0).any() or (idx > 0xFFFFFFFE).any():
+            raise _refuse("move_objects: indices must be object indices")
+        arrays = []
+        for name, a in (("position", position), ("rotation", rotation), ("scale", scale)):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != (idx.size, 3):
+                raise _refuse(f"move_objects: {name} must be {idx.size} x 3, not {a.shape}")
+            arrays.append(a)
+        idx = idx.astype(np.uint32)
+        fp = C.POINTER(C.c_float)
+        N.check_host(N.host().pth_renderer_move_objects(self._r, idx.size, idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                        *[a.ctypes.data_as(fp) for a in arrays]))
+
+    def object_transforms(self):
+        """(position, rotation, scale), each count x 3 float32: the transforms the current objects were made with, in
+        the scene file's order (rotation in radians)."""
+        n = int(N.host().pth_renderer_object_transforms(self._r, None, None, None))
+        out = [np.zeros((n, 3), dtype=np.float32) for _ in range(3)]
+        if n:
+            N.host().pth_renderer_object_transforms(self._r, *[a.ctypes.data_as(C.POINTER(C.c_float)) for a in out])
+        return tuple(out)
+
+    def rebuild_scene(self) -> None:
+        """A fresh SAH build of the current objects with the temporal history kept (pth_renderer_rebuild_scene): for
+        when a tree refitted by move_objects has grown slow.  Counts as the one move of its temporal step."""
+        self._single("rebuild_scene")
+        N.check_host(N.host().pth_renderer_rebuild_scene(self._r))
+
+    def refit_timing(self) -> float:
+        """hipEvent milliseconds of the last move_objects' kernels (pt_read_refit_timing)."""
+        self._single("refit_timing")
+        ms = C.c_float()
+        N.check_host(N.host().pth_renderer_refit_timing(self._r, C.byref(ms)))
+        return float(ms.value)
+
+    def bvh(self):
+        """(nodes, prims): the tree this object holds as PtBvhNode and PtHittable arrays -- the device's tree, after
+        move_objects the refitted one."""
+        nn, np_ = C.c_uint32(), C.c_uint32()
+        N.check_host(N.host().pth_renderer_bvh(self._r, None, None, C.byref(nn), C.byref(np_)))
+        nodes, prims = (PtBvhNode * max(1, nn.value))(), (PtHittable * max(1, np_.value))()
+        N.check_host(N.host().pth_renderer_bvh(self._r, nodes, prims, None, None))
+        return nodes, prims
 
     def holds_motion(self) -> bool:
         """Whether a motion table is held for the next temporal step (pt_holds_motion): from a load_scene_moved over a

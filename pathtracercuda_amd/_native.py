@@ -234,6 +234,13 @@ _HIP_SYMBOLS = {
     "pt_temporal_moments_motion_image": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32] + [P(C.c_float)] * 4 + [P(PtCamera)]
                                          + [P(C.c_float)] * 4 + [P(PtCamera), P(PtTemporalParams), P(PtVarianceParams)]
                                          + [P(C.c_float)] * 6 + [C.c_uint32, P(C.c_float), P(C.c_uint32)]),
+    "pt_set_primitive_boxes": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pt_holds_primitive_boxes": (C.c_int, [C.c_void_p]),
+    "pt_move_primitives": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint32), P(PtHittable), P(C.c_float), P(C.c_float),
+                                     P(C.c_uint32)]),
+    "pt_read_bvh": (C.c_int, [C.c_void_p, P(PtBvhNode), P(C.c_float)]),
+    "pt_read_primitive": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_float)]),
+    "pt_read_refit_timing": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "pt_group_create": (C.c_int, [C.c_int, P(C.c_int), C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_void_p)]),
     "pt_group_destroy": (None, [C.c_void_p]),
     "pt_group_size": (C.c_int, [C.c_void_p]),
@@ -277,6 +284,12 @@ _HOST_SYMBOLS = {
     "pth_renderer_load_scene_moved": (C.c_int, [C.c_void_p, C.c_char_p, P(C.c_uint32), P(PtCamera)]),
     "pth_renderer_holds_motion": (C.c_int, [C.c_void_p]),
     "pth_renderer_motion_table": (C.c_uint32, [C.c_void_p, P(P(C.c_float)), P(P(C.c_uint32))]),
+    "pth_renderer_move_objects": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint32), P(C.c_float), P(C.c_float), P(C.c_float)]),
+    "pth_renderer_rebuild_scene": (C.c_int, [C.c_void_p]),
+    "pth_renderer_object_transforms": (C.c_uint32, [C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float)]),
+    "pth_renderer_refit_timing": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "pth_renderer_bvh": (C.c_int, [C.c_void_p, P(PtBvhNode), P(PtHittable), P(C.c_uint32), P(C.c_uint32)]),
+    "pth_refit_boxes": (C.c_int, [P(PtBvhNode), C.c_uint32, P(C.c_float), C.c_uint32]),
     "pth_motion_table": (C.c_int, [P(PtHittable), P(PtHittable), C.c_uint32, P(C.c_float), P(C.c_uint32)]),
     "pth_renderer_render": (C.c_int, [C.c_void_p, P(PtCamera), C.c_uint32, C.c_uint32, C.c_int]),
     "pth_renderer_render_adaptive": (C.c_int, [C.c_void_p, P(PtCamera), P(PtAdaptiveParams), P(PtAdaptiveResult)]),

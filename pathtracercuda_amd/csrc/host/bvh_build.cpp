@@ -6,13 +6,18 @@
 #include <algorithm>
 #include <cfloat>
 #include <climits>
+#include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <atomic>
 #include <cstring>
 #include <future>
 #include <limits>
+#include <string>
 #include <thread>
+#include <vector>
 
+#include "host_internal.h"
 #include "pathtracer_amd.hpp"
 
 namespace {
@@ -215,4 +220,101 @@ uint32_t BVH::buildInto(std::vector<BVHNode>& out, size_t begin, size_t end)
     }
     out[nodeIndex] = node;
     return nodeIndex;
+}
+
+// ---- rule 10 of pt_hip.h on the host ---------------------------------------------------------------
+namespace ptamd {
+
+bool refitBoxes(pt_bvh_node* nodes, uint32_t nodeCount, const float* boxes, uint32_t primCount, std::string& error)
+{
+    if (!nodes || !boxes || nodeCount == 0 || primCount == 0) {
+        error = "refitBoxes: empty nodes or boxes";
+        return false;
+    }
+    char buf[160];
+    for (uint32_t i = 0; i < primCount; ++i)
+        for (int k = 0; k < 6; ++k) {
+            const float* b = boxes + 6 * (size_t)i;
+            if (!std::isfinite(b[k]) || (k < 3 && !(b[k] <= b[3 + k]))) {
+                snprintf(buf, sizeof(buf), "refitBoxes: primitive %u: box %s[%d] is not finite or min is above max", i,
+                         k < 3 ? "min" : "max", k % 3);
+                error = buf;
+                return false;
+            }
+        }
+    // the nodes reachable from the root, parents before their children
+    std::vector<uint32_t> order, st(1, 0u);
+    while (!st.empty()) {
+        const uint32_t i = st.back();
+        st.pop_back();
+        if (i >= nodeCount || order.size() >= nodeCount) {
+            error = "refitBoxes: the nodes are not a tree (a child index out of range, or a node reached twice)";
+            return false;
+        }
+        order.push_back(i);
+        const uint32_t count = nodes[i].primitive_count_axis >> 16;
+        if (count) {
+            if ((uint64_t)nodes[i].offset + count > primCount) {
+                error = "refitBoxes: a leaf's primitives are out of range";
+                return false;
+            }
+            continue;
+        }
+        if (nodes[i].offset <= i + 1) {
+            error = "refitBoxes: the nodes are not a tree (a second child not after its parent's first)";
+            return false;
+        }
+        st.push_back(i + 1);
+        st.push_back(nodes[i].offset);
+    }
+    for (size_t k = order.size(); k-- > 0;) {           // children before their parent
+        pt_bvh_node& n = nodes[order[k]];
+        const uint32_t count = n.primitive_count_axis >> 16;
+        if (count) {
+            const float* b = boxes + 6 * (size_t)n.offset;
+            for (int a = 0; a < 3; ++a) {
+                float lo = b[a], hi = b[3 + a];
+                for (uint32_t j = 1; j < count; ++j) {
+                    const float l = b[6 * (size_t)j + a], h = b[6 * (size_t)j + 3 + a];
+                    lo = l < lo ? l : lo;
+                    hi = h > hi ? h : hi;
+                }
+                n.aabb_min[a] = lo;
+                n.aabb_max[a] = hi;
+            }
+        } else {
+            const pt_bvh_node& A = nodes[order[k] + 1];
+            const pt_bvh_node& B = nodes[n.offset];
+            for (int a = 0; a < 3; ++a) {
+                n.aabb_min[a] = B.aabb_min[a] < A.aabb_min[a] ? B.aabb_min[a] : A.aabb_min[a];
+                n.aabb_max[a] = B.aabb_max[a] > A.aabb_max[a] ? B.aabb_max[a] : A.aabb_max[a];
+            }
+        }
+    }
+    return true;
+}
+
+} // namespace ptamd
+
+void BVH::refit(size_t count, const uint32_t* elementIndex, const CpuHittable* elements)
+{
+    for (size_t k = 0; k < count; ++k) m_elements[elementIndex[k]] = elements[k];
+    std::vector<pt_bvh_node> dn(m_nodes.size());
+    for (size_t i = 0; i < m_nodes.size(); ++i) dn[i] = ptamd::toDeviceNode(m_nodes[i]);
+    std::vector<float> boxes(6 * m_elements.size());
+    for (size_t i = 0; i < m_elements.size(); ++i) {
+        const AABB& b = m_elements[i].getAABB();
+        for (int a = 0; a < 3; ++a) {
+            boxes[6 * i + a] = b.m_min[a];
+            boxes[6 * i + 3 + a] = b.m_max[a];
+        }
+    }
+    std::string error;
+    if (!ptamd::refitBoxes(dn.data(), (uint32_t)dn.size(), boxes.data(), (uint32_t)m_elements.size(), error))
+        throw ptamd::Error(PT_ERR_STATE, error);
+    for (size_t i = 0; i < m_nodes.size(); ++i)
+        for (int a = 0; a < 3; ++a) {
+            m_nodes[i].m_aabb.m_min[a] = dn[i].aabb_min[a];
+            m_nodes[i].m_aabb.m_max[a] = dn[i].aabb_max[a];
+        }
 }

@@ -83,7 +83,8 @@ CpuHittable::CpuHittable()
 
 CpuHittable::CpuHittable(HittableType type, const vec3& position, const vec3& rotation, const vec3& scale,
                          const Material& material)
-    : m_invTransformRows{{1.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 1.0f, 0.0f}},
+    : m_position(position), m_rotation(rotation), m_scale(scale),
+      m_invTransformRows{{1.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 1.0f, 0.0f}},
       m_material(material),
       m_aabb{vec3(-1.0f), vec3(1.0f)},
       m_type(type)

@@ -306,6 +306,83 @@ PT_API uint32_t pth_renderer_motion_table(const pth_renderer* r, const float** r
     return n;
 }
 
+PT_API int pth_renderer_move_objects(pth_renderer* r, uint32_t count, const uint32_t* object, const float* position,
+                                     const float* rotation, const float* scale)
+{
+    if (!r) return setError(PT_ERR_ARG, "invalid argument");
+    if (count == 0 || !object || !position || !rotation || !scale)
+        return setError(PT_ERR_ARG, "pth_renderer_move_objects: count is 0 or an array is null");
+    PTH_GUARD_BEGIN
+    // moveObjects makes every check (a device group, no scene, an index out of range or given twice) before it reads a
+    // hittable; an index it will refuse gets a default object here, which nothing reads
+    const auto& objects = r->pt->sceneObjects();
+    std::vector<CpuHittable> moved;
+    moved.reserve(count);
+    for (uint32_t k = 0; k < count; ++k) {
+        if (object[k] >= objects.size()) {
+            moved.emplace_back();
+            continue;
+        }
+        const CpuHittable& o = objects[object[k]];
+        const float *p = position + 3 * (size_t)k, *q = rotation + 3 * (size_t)k, *s = scale + 3 * (size_t)k;
+        moved.emplace_back(o.type(), vec3(p[0], p[1], p[2]), vec3(q[0], q[1], q[2]), vec3(s[0], s[1], s[2]), o.material());
+    }
+    r->pt->moveObjects(count, object, moved.data());
+    return PT_OK;
+    PTH_GUARD_END
+}
+
+PT_API int pth_renderer_rebuild_scene(pth_renderer* r)
+{
+    if (!r) return setError(PT_ERR_ARG, "invalid argument");
+    PTH_GUARD_BEGIN
+    r->pt->rebuildScene();
+    return PT_OK;
+    PTH_GUARD_END
+}
+
+PT_API uint32_t pth_renderer_object_transforms(const pth_renderer* r, float* position, float* rotation, float* scale)
+{
+    if (!r) return 0;
+    const auto& objects = r->pt->sceneObjects();
+    for (size_t k = 0; k < objects.size(); ++k)
+        for (int a = 0; a < 3; ++a) {
+            if (position) position[3 * k + a] = objects[k].position()[a];
+            if (rotation) rotation[3 * k + a] = objects[k].rotation()[a];
+            if (scale) scale[3 * k + a] = objects[k].scale()[a];
+        }
+    return (uint32_t)objects.size();
+}
+
+PT_API int pth_renderer_refit_timing(pth_renderer* r, float* ms)
+{
+    if (!r || !ms) return setError(PT_ERR_ARG, "invalid argument");
+    PTH_GUARD_BEGIN
+    *ms = r->pt->refitTiming();
+    return PT_OK;
+    PTH_GUARD_END
+}
+
+PT_API int pth_renderer_bvh(const pth_renderer* r, pt_bvh_node* nodes, pt_hittable* prims, uint32_t* node_count,
+                            uint32_t* prim_count)
+{
+    if (!r) return setError(PT_ERR_ARG, "invalid argument");
+    const auto& bn = r->pt->bvh().getNodes();
+    const auto& be = r->pt->bvh().getElements();
+    if (node_count) *node_count = (uint32_t)bn.size();
+    if (prim_count) *prim_count = (uint32_t)be.size();
+    for (size_t i = 0; nodes && i < bn.size(); ++i) nodes[i] = ptamd::toDeviceNode(bn[i]);
+    for (size_t i = 0; prims && i < be.size(); ++i) prims[i] = be[i].getGpuHittable();
+    return PT_OK;
+}
+
+PT_API int pth_refit_boxes(pt_bvh_node* nodes, uint32_t node_count, const float* boxes, uint32_t prim_count)
+{
+    std::string error;
+    if (!ptamd::refitBoxes(nodes, node_count, boxes, prim_count, error)) return setError(PT_ERR_ARG, error.c_str());
+    return PT_OK;
+}
+
 PT_API int pth_motion_table(const pt_hittable* prev, const pt_hittable* cur, uint32_t count, float* rows, uint32_t* valid)
 {
     if (count && (!prev || !cur || !rows || !valid)) return setError(PT_ERR_ARG, "pth_motion_table: an array is null");

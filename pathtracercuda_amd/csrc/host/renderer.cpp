@@ -211,6 +211,88 @@ void Pathtracer::setSceneMoved(size_t count, const CpuHittable* hittables, const
     m_upsampled = false;
 }
 
+void Pathtracer::moveObjects(size_t count, const uint32_t* object, const CpuHittable* hittables)
+{
+    if (m_group) check(PT_ERR_STATE, "moveObjects: not available on a device group");
+    if (m_sceneObjects.empty()) refuse(PT_ERR_STATE, "moveObjects: no scene is set");
+    if (count == 0 || !object || !hittables) refuse(PT_ERR_ARG, "moveObjects: count is 0 or an array is null");
+    const size_t n = m_sceneObjects.size();
+    char msg[200];
+    std::vector<char> seen(n, 0);
+    for (size_t k = 0; k < count; ++k) {
+        if (object[k] >= n) {
+            snprintf(msg, sizeof(msg), "moveObjects: object[%zu] = %u is not below the scene's %zu objects", k, object[k], n);
+            refuse(PT_ERR_ARG, msg);
+        }
+        if (seen[object[k]]) {
+            snprintf(msg, sizeof(msg), "moveObjects: object %u is given twice", object[k]);
+            refuse(PT_ERR_ARG, msg);
+        }
+        seen[object[k]] = 1;
+    }
+    std::vector<uint32_t> index(count), prev(count);
+    std::vector<pt_hittable> dp(count);
+    std::vector<float> boxes(6 * count), rows(12 * count);
+    for (size_t k = 0; k < count; ++k) {
+        index[k] = m_objectToPrim[object[k]];
+        dp[k] = hittables[k].getGpuHittable();
+        const AABB& b = hittables[k].getAABB();
+        for (int a = 0; a < 3; ++a) {
+            boxes[6 * k + a] = b.m_min[a];
+            boxes[6 * k + 3 + a] = b.m_max[a];
+        }
+        const bool ok = ptamd::motionRows(m_sceneObjects[object[k]].invTransformRows(), hittables[k].invTransformRows(), &rows[12 * k]);
+        prev[k] = ok ? index[k] : 0xffffffffu;
+    }
+    if (!pt_holds_primitive_boxes(m_ctx)) {          // the first move, or the first since a scene or texture change
+        const auto& elems = m_bvh.getElements();
+        std::vector<float> all(6 * elems.size());
+        for (size_t i = 0; i < elems.size(); ++i) {
+            const AABB& b = elems[i].getAABB();
+            for (int a = 0; a < 3; ++a) {
+                all[6 * i + a] = b.m_min[a];
+                all[6 * i + 3 + a] = b.m_max[a];
+            }
+        }
+        check(pt_set_primitive_boxes(m_ctx, all.data()), "pt_set_primitive_boxes");
+    }
+    check(pt_move_primitives(m_ctx, (uint32_t)count, index.data(), dp.data(), boxes.data(), rows.data(), prev.data()),
+          "pt_move_primitives");
+    // accepted: this class mirrors what the device holds now
+    m_bvh.refit(count, index.data(), hittables);
+    for (size_t k = 0; k < count; ++k) m_sceneObjects[object[k]] = hittables[k];
+    const size_t np = m_bvh.getElements().size();
+    m_motionRows.assign(12 * np, 0.0f);
+    m_motionPrev.resize(np);
+    for (size_t p = 0; p < np; ++p) {
+        m_motionRows[12 * p] = m_motionRows[12 * p + 5] = m_motionRows[12 * p + 10] = 1.0f;
+        m_motionPrev[p] = (uint32_t)p;
+    }
+    for (size_t k = 0; k < count; ++k) {
+        memcpy(&m_motionRows[12 * (size_t)index[k]], &rows[12 * k], 12 * sizeof(float));
+        m_motionPrev[index[k]] = prev[k];
+    }
+    m_denoised = false;
+    m_despiked = false;
+    m_upsampled = false;
+}
+
+void Pathtracer::rebuildScene()
+{
+    if (m_group) check(PT_ERR_STATE, "rebuildScene: not available on a device group");
+    if (m_sceneObjects.empty()) refuse(PT_ERR_STATE, "rebuildScene: no scene is set");
+    const std::vector<CpuHittable> objects = m_sceneObjects;
+    setSceneMoved(objects.size(), objects.data());
+}
+
+float Pathtracer::refitTiming()
+{
+    if (m_group) check(PT_ERR_STATE, "refitTiming: not available on a device group");
+    float ms[3] = {};
+    check(pt_read_refit_timing(m_ctx, ms), "pt_read_refit_timing");
+    return ms[0];
+}
+
 bool Pathtracer::holdsMotion() const { return !m_group && pt_holds_motion(m_ctx) != 0; }
 
 void Pathtracer::render(const Camera& camera, uint32_t spp, bool ignoreHistory)

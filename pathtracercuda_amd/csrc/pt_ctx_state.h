@@ -1,6 +1,6 @@
 // pt_ctx_state.h -- what a context carries from one call to the next, and every rule that moves it:
 // no HIP call, no context, plain values.  The C ABI functions (pt_kernels.hip, pt_denoise.h, pt_temporal.h, pt_svgf.h,
-// pt_adaptive_variance.h, pt_despike.h, pt_upsample.h)
+// pt_adaptive_variance.h, pt_despike.h, pt_upsample.h, pt_refit.h)
 // raise the events below and ask the predicates; they assign none of these fields themselves.
 // tools/ctx_state_check.cpp and tests/test_ctx_state.py run the same functions on the CPU.
 //
@@ -59,6 +59,11 @@
 //                   larger frame: ended when a pt_upsample has passed its checks, set when it is done (dnValid's rule: the
 //                   image is a result handed out, and what it was made from may move on).  Nothing else ends it, and
 //                   the context of the smaller frame raises no event.
+//   boxValid        "the per-primitive boxes and the refit lists are of the current scene" (rule 10 of include/pt_hip.h;
+//                   pt_holds_primitive_boxes, and pt_move_primitives asks for it): set by pt_set_primitive_boxes, ended
+//                   by a scene or texture change, kept by a move (primitives_moved), which keeps the topology and
+//                   replaces the boxes of what it moves.  A texture change ends it too although it touches no box:
+//                   that costs one more pt_set_primitive_boxes and spares a second event.  Tied to no other fact.
 //   epoch           counts the launches that wrote the accumulation (a device group's gather cache
 //                   key, pt_group.h).  Never decreases.
 // A call refused for its arguments or for the state raises no event (but for a render whose plan is a
@@ -86,6 +91,7 @@ struct CtxState {
     bool dsValid = false;
     bool motionValid = false;
     bool usValid = false;
+    bool boxValid = false;
     uint64_t epoch = 0;
 };
 
@@ -100,6 +106,7 @@ inline void scene_or_texture_changed(CtxState& s)
     s.momValid = false;
     s.dsValid = false;
     s.motionValid = false;
+    s.boxValid = false;
     ++s.stateEpoch;
 }
 
@@ -113,6 +120,19 @@ inline void scene_moved(CtxState& s)
     s.histValid = hist;
     s.momValid = mom;
     s.motionValid = hist;
+}
+
+// pt_set_primitive_boxes
+inline void boxes_set(CtxState& s) { s.boxValid = true; }
+
+// pt_move_primitives: scene_moved when the move comes with a motion table, a scene change when it does not; either
+// way the boxes stay, because the move has replaced those of what it moved and the topology is what it was
+inline void primitives_moved(CtxState& s, bool with_table)
+{
+    const bool boxes = s.boxValid;
+    if (with_table) scene_moved(s);
+    else scene_or_texture_changed(s);
+    s.boxValid = boxes;
 }
 
 // pt_set_skybox while `held` is set: only another handle changes anything (the planes hold first hits: no
@@ -256,5 +276,6 @@ inline bool variance_of_counts(const CtxState& s) { return s.avValid; }
 inline bool holds_despiked(const CtxState& s) { return s.dsValid; }
 inline bool holds_motion(const CtxState& s) { return s.motionValid; }
 inline bool holds_upsampled(const CtxState& s) { return s.usValid; }
+inline bool holds_boxes(const CtxState& s) { return s.boxValid; }
 
 } // namespace pt

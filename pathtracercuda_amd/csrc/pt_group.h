@@ -97,6 +97,7 @@ PT_API int pt_group_create(int ndev, const int* devices, uint32_t width, uint32_
         pt_context* c = nullptr;
         const int rc = pt_create_banded(devices[i], width, height, band_rows, (uint32_t)i, (uint32_t)ndev, &c);
         if (rc != PT_OK) return bail(rc);
+        c->grouped = true;
         g->ctx.push_back(c);
         g->stageOff.push_back(staged);
         staged += (size_t)c->rows * width;

@@ -457,6 +457,8 @@ __global__ void __launch_bounds__(256) adapt_scatter_kernel(const unsigned long 
 
 #include "pt_dev_upsample_resolve.h"
 
+#include "pt_dev_refit.h"
+
 // Multi-device gather, second half: scatter one device's received rows (its bands, in local row
 // order) into the full image.  A band is band-rows consecutive image rows in both buffers, so every
 // lane copies one float4 of a coalesced row.
@@ -586,6 +588,18 @@ struct pt_context {
     hipEvent_t usEv[3] = {};          // before the flat pass, between the kernels, after upsample_kernel
     float usMs[2] = {};
     uint32_t usCounts[2] = {};        // guided pixels that needed ring 2, that took the nearest low pixel
+    // moving primitives and the refit (pt_refit.h); the boxes and lists are of the scene while holds_boxes
+    bool grouped = false;             // a member of a device group (pt_group_create): the refit is refused there
+    float4* rfBoxes = nullptr;        // [primCount][2]: min xyz, max xyz (w = 0)
+    uint32_t* rfLists = nullptr;      // the reachable leaves' node indices, then (node, record) per interior node by depth
+    uint32_t rfLeafCount = 0;
+    std::vector<uint32_t> rfLevelOff; // interior depth d (the root's is 0) holds pairs rfLevelOff[d] .. rfLevelOff[d + 1]
+    float4* rfPack = nullptr;         // the packed records of a move, kMoveQuads each
+    size_t rfPackCap = 0;             // moved primitives it was made for
+    std::vector<float4> rfHost;       // the same on the host, kept until the copy is done
+    hipEvent_t rfEv[3] = {};          // before and after the kernels of a move; [2] before the copy
+    float rfMs = 0.0f, rfPackMs = 0.0f, rfCopyMs = 0.0f;   // the kernels, the host packing, the copy
+    bool rfRan = false;               // a move has run on this context
     std::string err;
 };
 
@@ -896,6 +910,11 @@ PT_API void pt_destroy(pt_context* ctx)
     (void)hipFree(ctx->avBuf);
     (void)hipFree(ctx->dsBuf);
     (void)hipFree(ctx->usBuf);
+    (void)hipFree(ctx->rfBoxes);
+    (void)hipFree(ctx->rfLists);
+    (void)hipFree(ctx->rfPack);
+    for (auto& e : ctx->rfEv)
+        if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->dnEv)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->tmEv)
@@ -932,6 +951,24 @@ static std::vector<float4> motion_table_pack(uint32_t prim_count, const float* r
         e[4 * (size_t)i + 3] = make_float4(u2f(prev_index[i]), 0.0f, 0.0f, 0.0f);
     }
     return e;
+}
+
+// A primitive's four quads and its material's three as the kernels read them (pt_set_scene and pt_move_primitives).
+static void pack_primitive(const pt_context* ctx, const pt_hittable& h, float4* p, float4* m)
+{
+    const float(&R)[3][4] = h.inv_transform_rows;
+    p[0] = make_float4(R[0][0], R[1][0], R[0][1], R[1][1]);
+    p[1] = make_float4(R[0][2], R[1][2], R[0][3], R[1][3]);
+    p[2] = make_float4(R[2][0], R[2][1], R[2][2], R[2][3]);
+    // fourth quad: the type and the shape's quadric constants (quadric_roots reads them here)
+    float qB, qH, qJ;
+    quadric_consts(h.type, qB, qH, qJ);
+    if ((int)h.type == ctx->zeroConstsType)                      // test knob, see pt_hip.h: zeros for a
+        qB = qH = qJ = (h.type == 2u || h.type >= 5u) ? std::nanf("") : 0.0f;   // quadric, NaN for a plane or cube
+    p[3] = make_float4(u2f(h.type), qB, qH, qJ);
+    m[0] = make_float4(h.base_color[0], h.base_color[1], h.base_color[2], h.roughness);
+    m[1] = make_float4(h.emissive[0], h.emissive[1], h.emissive[2], h.metalness);
+    m[2] = make_float4(u2f(h.texture_index), u2f(h.material_type), 0.0f, 0.0f);
 }
 
 // Host-side validation of the BVH so a malformed scene can never make the kernel read out of
@@ -1060,22 +1097,7 @@ static int set_scene_impl(pt_context* ctx, const pt_bvh_node* nodes, uint32_t no
         q[3] = make_float4(u2f(word(i + 1)), u2f(word(nodes[i].offset)), u2f(1u << ((nodes[i].primitive_count_axis >> 8) & 0xffu)),
                            u2f(firstPrim[nodes[i].offset]));
     }
-    for (uint32_t i = 0; i < prim_count; ++i) {
-        const pt_hittable& h = prims[i];
-        const float(&R)[3][4] = h.inv_transform_rows;
-        hp[4 * i + 0] = make_float4(R[0][0], R[1][0], R[0][1], R[1][1]);
-        hp[4 * i + 1] = make_float4(R[0][2], R[1][2], R[0][3], R[1][3]);
-        hp[4 * i + 2] = make_float4(R[2][0], R[2][1], R[2][2], R[2][3]);
-        // fourth quad: the type and the shape's quadric constants (quadric_roots reads them here)
-        float qB, qH, qJ;
-        quadric_consts(h.type, qB, qH, qJ);
-        if ((int)h.type == ctx->zeroConstsType)                      // test knob, see pt_hip.h: zeros for a
-            qB = qH = qJ = (h.type == 2u || h.type >= 5u) ? std::nanf("") : 0.0f;   // quadric, NaN for a plane or cube
-        hp[4 * i + 3] = make_float4(u2f(h.type), qB, qH, qJ);
-        hm[3 * i] = make_float4(h.base_color[0], h.base_color[1], h.base_color[2], h.roughness);
-        hm[3 * i + 1] = make_float4(h.emissive[0], h.emissive[1], h.emissive[2], h.metalness);
-        hm[3 * i + 2] = make_float4(u2f(h.texture_index), u2f(h.material_type), 0.0f, 0.0f);
-    }
+    for (uint32_t i = 0; i < prim_count; ++i) pack_primitive(ctx, prims[i], &hp[4 * (size_t)i], &hm[3 * (size_t)i]);
     PT_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     PT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     (void)hipFree(ctx->nodes);
@@ -2090,6 +2112,8 @@ PT_API int pt_set_kernel_variant(pt_context* ctx, int variant)
 #include "pt_upsample.h"
 
 #include "pt_upsample_resolve.h"
+
+#include "pt_refit.h"
 
 extern "C" PT_API const char* pt_last_error(const pt_context* ctx)
 {

@@ -7,7 +7,8 @@
 //   <event> [key=value ...]     an event of the header by name; render_begins takes cam=ID (a small integer
 //                               the tool turns into distinct pt_camera bytes) and adds "stashMatches" and
 //                               "misses" to the object, order_sorted takes samples= and strip=, sky_set takes held= and
-//                               handle=
+//                               handle=; primitives_moved(s, with_table) is primitives_moved_with_table and
+//                               primitives_moved_without_table
 //   <predicate>                 a predicate of the header by name; adds "result"
 //   fuzz seed=S n=N             N seeded random events on a fresh state; adds "violations", the number of
 //                               times one of the invariants of Fuzz::step did not hold
@@ -40,31 +41,39 @@ static pt_camera camera_of(unsigned long long id)
     return c;
 }
 
+// primitives_moved takes an argument: the lists below hold its two forms
+static void primitives_moved_with_table(CtxState& s) { primitives_moved(s, true); }
+static void primitives_moved_without_table(CtxState& s) { primitives_moved(s, false); }
+
 static void (*const kEventFns[])(CtxState&) = {
     scene_or_texture_changed, rng_written, schedule_changed, order_dropped, order_replaced, order_biased,
     accum_written, stash_made, adaptive_begins, adaptive_done, features_begin, features_done, denoise_begins, denoise_done,
     temporal_begins, temporal_done, moments_done, adaptive_variance_begins, adaptive_variance_done, despike_begins,
-    despike_done, scene_moved, upsample_begins, upsample_done};
+    despike_done, scene_moved, upsample_begins, upsample_done, boxes_set, primitives_moved_with_table,
+    primitives_moved_without_table};
 static const char* const kEventNames[] = {
     "scene_or_texture_changed", "rng_written", "schedule_changed", "order_dropped", "order_replaced",
     "order_biased", "accum_written", "stash_made", "adaptive_begins", "adaptive_done", "features_begin", "features_done",
     "denoise_begins", "denoise_done", "temporal_begins", "temporal_done", "moments_done", "adaptive_variance_begins",
     "adaptive_variance_done", "despike_begins", "despike_done", "scene_moved", "upsample_begins",
-    "upsample_done"};
+    "upsample_done", "boxes_set", "primitives_moved_with_table", "primitives_moved_without_table"};
 constexpr int kEvents = sizeof(kEventFns) / sizeof(kEventFns[0]);
 // the tool's own list of the events after which a sample is no longer what the last render's was
 static bool moves_epoch(void (*event)(CtxState&))
 {
-    return event == scene_or_texture_changed || event == rng_written || event == adaptive_begins || event == scene_moved;
+    return event == scene_or_texture_changed || event == rng_written || event == adaptive_begins || event == scene_moved ||
+           event == primitives_moved_with_table || event == primitives_moved_without_table;
 }
 static_assert(kEvents == sizeof(kEventNames) / sizeof(kEventNames[0]), "one name per event");
 
 static bool (*const kPredicates[])(const CtxState&) = {counts_describe_buffer, moments_continue, planes_current, holds_denoised,
                                                        holds_temporal, history_held, temporal_of_planes, history_has_moments,
-                                                       variance_of_counts, holds_despiked, holds_motion, holds_upsampled};
+                                                       variance_of_counts, holds_despiked, holds_motion, holds_upsampled,
+                                                       holds_boxes};
 static const char* const kPredicateNames[] = {"counts_describe_buffer", "moments_continue", "planes_current", "holds_denoised",
                                               "holds_temporal", "history_held", "temporal_of_planes", "history_has_moments",
-                                              "variance_of_counts", "holds_despiked", "holds_motion", "holds_upsampled"};
+                                              "variance_of_counts", "holds_despiked", "holds_motion", "holds_upsampled",
+                                              "holds_boxes"};
 constexpr int kPredicateCount = sizeof(kPredicates) / sizeof(kPredicates[0]);
 static_assert(kPredicateCount == sizeof(kPredicateNames) / sizeof(kPredicateNames[0]), "one name per predicate");
 
@@ -97,6 +106,7 @@ struct Fuzz {
         const bool ds = s.dsValid, feat = s.featValid;
         const bool motion = s.motionValid;
         const bool us = s.usValid;
+        const bool boxes = s.boxValid;
         const uint32_t e = next() % (kEvents + 6);       // (a render as likely as four other events)
         if (e < (uint32_t)kEvents) {
             kEventFns[e](s);
@@ -131,8 +141,11 @@ struct Fuzz {
         // the tool's own list of what ends a history and what does not
         if (e < (uint32_t)kEvents) {
             void (*const f)(CtxState&) = kEventFns[e];
+            // a move of primitives is, for every fact but the boxes, the scene event it stands for
+            const bool moved = f == scene_moved || f == primitives_moved_with_table;
+            const bool changed = f == scene_or_texture_changed || f == primitives_moved_without_table;
             // (a move ends the history only when it is the second one since a temporal pass)
-            const bool ends = f == scene_or_texture_changed || f == temporal_begins || (f == scene_moved && motion);
+            const bool ends = changed || f == temporal_begins || (moved && motion);
             if (f != temporal_done) check(s.histValid == (hist && !ends));
             if (f == features_begin) check(!s.tpOfPlanes);
             // the moments end with the history (a plain temporal step begins as every step and sets them no more);
@@ -147,23 +160,28 @@ struct Fuzz {
             // render is checked above), a features call that begins, a scene or texture change (another sky is checked
             // above); only a finished pt_despike over current planes sets it
             const bool endsDs = f == despike_begins || f == adaptive_begins || f == features_begin ||
-                                f == scene_or_texture_changed || f == scene_moved;
+                                changed || moved;
             check(s.dsValid == (f == despike_done ? feat : (ds && !endsDs)));
             // the tool's own list of what ends the motion table: a temporal pass that begins, a scene or texture change
             // (another sky is checked above), a second move; only a first move over a held history sets it
-            const bool endsMotion = f == temporal_begins || f == scene_or_texture_changed;
-            check(s.motionValid == (f == scene_moved ? (hist && !motion) : (motion && !endsMotion)));
+            const bool endsMotion = f == temporal_begins || changed;
+            check(s.motionValid == (moved ? (hist && !motion) : (motion && !endsMotion)));
             // the tool's own list for the upsampled image: only the call's own two events move it
             check(s.usValid == (f == upsample_done ? true : (us && f != upsample_begins)));
-            if (f == scene_moved) check(!s.featValid && s.stateEpoch == stateEpoch + 1 && s.order.stale);
+            if (moved || changed) check(!s.featValid && s.stateEpoch == stateEpoch + 1 && s.order.stale);
+            // the tool's own list for the boxes: set by their upload, ended by a scene or texture change and by a scene
+            // that comes with a table; a move of primitives keeps them
+            check(s.boxValid == (f == boxes_set ? true : (boxes && f != scene_or_texture_changed && f != scene_moved)));
         } else if (e != (uint32_t)kEvents + 1) {
             check(s.histValid == hist && s.momValid == mom);     // a sort of the order, a render
             check(s.motionValid == motion);
             check(s.usValid == us);                              // (a render ends no upsampled image)
+            check(s.boxValid == boxes);
             if (e == (uint32_t)kEvents) check(s.avValid == av && s.dsValid == ds);
         } else {
             check(s.avValid == av);                              // a sky ends no variance of the counts
             check(s.usValid == us);                              // nor an upsampled image
+            check(s.boxValid == boxes);                          // nor the boxes
         }
         check(s.stateEpoch >= stateEpoch && s.epoch >= epoch);
         check(s.aheadMisses <= 1000u);
@@ -176,12 +194,12 @@ static void print_state(const CtxState& s, const std::string& extra)
            "\"lastState\": %llu, \"launched\": %d, \"lastCam\": %d, \"aheadValid\": %d, \"aheadMisses\": %u, \"adMomValid\": %d, "
            "\"adCountsValid\": %d, \"featValid\": %d, \"dnValid\": %d, \"tpValid\": %d, \"histValid\": %d, "
            "\"tpOfPlanes\": %d, \"momValid\": %d, \"avValid\": %d, \"dsValid\": %d, \"motionValid\": %d, "
-           "\"usValid\": %d, \"epoch\": %llu%s}\n",
+           "\"usValid\": %d, \"boxValid\": %d, \"epoch\": %llu%s}\n",
            (int)s.order.valid, (int)s.order.stale, (unsigned long long)s.order.samples, s.order.strip,
            (unsigned long long)s.stateEpoch, (unsigned long long)s.lastState, (int)s.launched, (int)s.lastCam.origin[0],
            (int)s.aheadValid, s.aheadMisses, (int)s.adMomValid, (int)s.adCountsValid, (int)s.featValid, (int)s.dnValid,
            (int)s.tpValid, (int)s.histValid, (int)s.tpOfPlanes, (int)s.momValid, (int)s.avValid, (int)s.dsValid,
-           (int)s.motionValid, (int)s.usValid, (unsigned long long)s.epoch, extra.c_str());
+           (int)s.motionValid, (int)s.usValid, (int)s.boxValid, (unsigned long long)s.epoch, extra.c_str());
     fflush(stdout);
 }
 
